@@ -8,9 +8,15 @@ camera x 500 frames, 50k bundles, 4-frame tracks, 152,991 parameters).  One
 step = one full LM solve of the scene from its initial guess, with the problem
 already resident in HBM (the plan is uploaded before the timed region); every
 solve hands errorList / ud->errorList / errorDistanceList back to the caller's
-page-locked host buffers, as the seam's caller needs them.  The same solves
-leaving those outputs in HBM (mmba_plan_outputs) are timed beside it
-(`device_resident`).
+page-locked host buffers, as the seam's caller needs them.
+
+A plain run sets up, warms up, times the steps and prints the result line.
+`--dump-outputs DIR` also writes what the last timed solve handed back
+(DIR/<name>.npy).  Everything else is measured only with `--full`: the same
+solves leaving those outputs in HBM (mmba_plan_outputs; `device_resident`),
+the kernel statistics behind `roofline` / `reduced_cholesky` (separate solves
+under HIP events), the rocprofv3 PMC passes (`roofline.traffic`) and the CPU
+baseline.  Without `--full` those entries of the line are null.
 
 `value` is whole-job residuals/s: observations x (residual evaluations +
 Jacobian evaluations) per second (SURVEY 8(d) metric definitions); LM
@@ -85,15 +91,28 @@ def parse():
     ap.add_argument("--per-frame", type=int, default=0, metavar="CONC",
                     help="per-frame solve mode (mmba_solve_per_frame) with CONC frames at "
                          "once; prints its own JSON line (not the headline metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the "
+                         "device-resident rate, kernel statistics (roofline, reduced_cholesky), "
+                         "the rocprofv3 PMC passes and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed solve handed back "
+                         "as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget-s", type=float, default=30.0,
                     help="skip the larger CPU window once this much CPU time is spent")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the rocprofv3 PMC passes that fill roofline.traffic")
+                    help="with --full: skip the rocprofv3 PMC passes that fill roofline.traffic")
     ap.add_argument("--path", action="append", default=[], metavar="NAME=VALUE",
                     help="A/B diagnostics: pin a plan-builder choice through the "
                          "mmba_debug_set_path test hook (e.g. pcr=0); the line records it")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def apply_paths(args):
@@ -179,7 +198,7 @@ def pmc_traffic(args):
     prof = shutil.which("rocprofv3")
     if prof is None:
         return None, "rocprofv3 not found"
-    base = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0",
+    base = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--full",
             "--no-cpu-baseline", "--no-traffic", "--config", str(args.config),
             "--scale", str(args.scale)]
     if args.frames:
@@ -410,11 +429,16 @@ def per_frame_line(args):
     t0 = time.perf_counter()
     resid = iters = 0
     for _ in range(args.steps):
-        _, res = step()
+        x, res = step()
         for f, r in enumerate(res):
             resid += int(obs_per_frame[f]) * (r["function_evals"] + r["outer_iterations"])
             iters += r["outer_iterations"]
     dt = time.perf_counter() - t0
+    if args.dump_outputs:  # what the last call handed back: x and the per-frame RMS
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "x.npy"), np.asarray(x, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "frame_error_rms.npy"),
+                np.array([r["error_rms"] for r in res], dtype=np.float64))
     rms = float(np.sqrt(np.mean([r["error_rms"] ** 2 for r in res if r["success"]])))
     print(json.dumps({
         "metric": "per-frame solve mode residuals/s", "value": resid / dt,
@@ -428,6 +452,37 @@ def per_frame_line(args):
         flush=True)
     if sv is not None:
         sv.close()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, prob, last, outs):
+    """--dump-outputs: what the last timed solve handed back to its caller, one
+    float64 DIR/<name>.npy each: the solved x, errorList / ud->errorList /
+    errorDistanceList as the caller's buffers hold them, the ||f|| trace and
+    the numeric fields of the result record.  Outputs that together exceed
+    64 MB (many-GPU scenes) are cut to a fixed, seeded sample of their entries,
+    whose indices are written beside them."""
+    m, M = prob.num_residuals, prob.num_obs
+    rec = {k: v for k, v in sorted(last.result.items())
+           if isinstance(v, (bool, int, float)) and not k.startswith("time_")}
+    arrays = {"x": last.x, "error_list": outs[0][:m], "error_list_user": outs[1][:m],
+              "error_distance_list": outs[2][:M], "fnorm_trace": last.fnorm_trace,
+              "result": np.array(list(rec.values()), dtype=np.float64)}
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(8 * a.size for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if total > DUMP_LIMIT_BYTES // 2:  # the sample's indices are stored too
+            keep = max(1, int(a.size * (DUMP_LIMIT_BYTES // 2) / (2.0 * total)))
+            rng = np.random.Generator(np.random.PCG64(20241008))
+            idx = np.sort(rng.choice(a.size, size=min(keep, a.size), replace=False))
+            np.save(os.path.join(outdir, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+    with open(os.path.join(outdir, "result_fields.json"), "w") as f:
+        json.dump(list(rec.keys()), f)
 
 
 def parallelism(world, group, devices):
@@ -454,7 +509,7 @@ def main():
     # PMC passes first, as child processes, before this process initialises
     # the GPU (rank 0 of a 1-GPU run only)
     traffic, traffic_detail = None, None
-    if nshards == 1 and not args.no_traffic:
+    if args.full and nshards == 1 and not args.no_traffic:
         traffic, traffic_detail = pmc_traffic(args)
     from mayamatchmovesolver_amd import synthetic as S
     from mayamatchmovesolver_amd.solver import Comm, Context, Solver, comm_unique_id
@@ -529,31 +584,32 @@ def main():
     dt = time.perf_counter() - t0
     dt_max = allreduce(dist, dt, "max")
     dt_ranks = allgather_float(dist, dt)  # per-shard times (the max is the value's clock)
-    # device-resident rate (reported beside value, never as value): the same
-    # solves leaving the per-residual outputs in HBM (mmba_plan_solve with
-    # NULL output pointers; mmba_plan_outputs fetches them on demand)
-    barrier(dist)
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    for st in range(args.steps):
-        solver.solve(fetch=False)
-        progress("device-resident step %d/%d" % (st + 1, args.steps))
-    ctx.synchronize()
-    barrier(dist)
-    dt_dev = allreduce(dist, time.perf_counter() - t0, "max")
-    # kernel timing (HIP events around the spans) on separate, untimed
-    # solves, so the events do not weigh on the timed steps
-    solver.set_timing(True)
-    for _ in range(max(1, min(args.steps, 5))):
-        solver.solve(out=outs)
-    stats = solver.kernel_stats()
-    solver.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, prob, last, outs)
+    dt_dev = stats = None
+    if args.full:
+        # device-resident rate (reported beside value, never as value): the
+        # same solves leaving the per-residual outputs in HBM (mmba_plan_solve
+        # with NULL output pointers; mmba_plan_outputs fetches them on demand)
+        barrier(dist)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        for st in range(args.steps):
+            solver.solve(fetch=False)
+            progress("device-resident step %d/%d" % (st + 1, args.steps))
+        ctx.synchronize()
+        barrier(dist)
+        dt_dev = allreduce(dist, time.perf_counter() - t0, "max")
+        # kernel timing (HIP events around the spans) on separate, untimed
+        # solves, so the events do not weigh on the timed steps
+        solver.set_timing(True)
+        for _ in range(max(1, min(args.steps, 5))):
+            solver.solve(out=outs)
+        stats = solver.kernel_stats()
+        solver.set_timing(False)
 
-    if rank == 0:
-        # one solve of the whole scene per step: count observations once
-        resid = float(prob.num_obs) * (nfev + njev)
-        value = resid / dt_max
-        lm_rate = iters / dt_max
+    roofline = chol = cpu = None
+    if rank == 0 and args.full:
         # Roofline: the FD-Jacobian + normal-equation pass (HBM class) on this
         # rank's shard, bytes = B_J x observations per launch
         jac_ms = stats["jac_ms_avg"]
@@ -638,9 +694,13 @@ def main():
                             "avg_ms": stats["chol_ms_avg"], "flops_per_launch":
                             stats["chol_flops"], "launches": stats["chol_launches"],
                             "k2_hbm": roofline}
-        cpu = None
         if not args.no_cpu_baseline and nshards == 1:
             cpu = cpu_baseline(args.config, args.cpu_budget_s, ctx)
+    if rank == 0:
+        # one solve of the whole scene per step: count observations once
+        resid = float(prob.num_obs) * (nfev + njev)
+        value = resid / dt_max
+        lm_rate = iters / dt_max
         r = last.result
         line = {
             "metric": "LM iterations/sec + residuals/sec (markers x frames) at 1/2/4/8 MI355X; "
@@ -676,7 +736,8 @@ def main():
                         "errorDistanceList in HBM (mmba_plan_outputs); not the value",
                 "ms_per_step": 1e3 * dt_dev / args.steps,
                 "value": resid / dt_dev,
-                "lm_iterations_per_s": iters / dt_dev},
+                "lm_iterations_per_s": iters / dt_dev} if args.full else None,
+            "full": args.full,
             "lm_iterations_per_solve": r["outer_iterations"],
             "nfev_per_solve": r["iterations"],
             "reason_number": r["reason_number"],

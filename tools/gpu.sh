@@ -38,7 +38,7 @@ for step in "$@"; do
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { cat "$OUT/smoke.log"; exit 1; } ;;
     bench)
-      timeout -k 10 500 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
+      timeout -k 10 500 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail "$OUT/bench.err"; exit 1; }
       cat "$OUT/bench.json" ;;
     benchcfg:*)
       c=${step#benchcfg:}
@@ -46,15 +46,15 @@ for step in "$@"; do
       if [ "$c" = 2 ]; then st=3; wu=1; fi  # C3: ~11 s per solve
       cb=--no-cpu-baseline
       if [ "$c" = 1 ] || [ "$c" = 4 ]; then cb=; fi  # C2 / C5: the CPU windows + the full-config oracle run
-      timeout -k 10 600 python -u bench.py --config "$c" --steps $st --warmup $wu $cb --no-traffic > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { tail "$OUT/bench_$c.err"; exit 1; }
+      timeout -k 10 600 python -u bench.py --config "$c" --steps $st --warmup $wu --full $cb --no-traffic > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { tail "$OUT/bench_$c.err"; exit 1; }
       cat "$OUT/bench_$c.json" ;;
     benchpath:*)
       pv=${step#benchpath:}
-      timeout -k 10 400 python -u bench.py --path "$pv" --steps 8 --warmup 3 --no-cpu-baseline --no-traffic > "$OUT/bench_$pv.json" 2> "$OUT/bench_$pv.err" || { tail "$OUT/bench_$pv.err"; exit 1; }
+      timeout -k 10 400 python -u bench.py --path "$pv" --steps 8 --warmup 3 --full --no-cpu-baseline --no-traffic > "$OUT/bench_$pv.json" 2> "$OUT/bench_$pv.err" || { tail "$OUT/bench_$pv.err"; exit 1; }
       cat "$OUT/bench_$pv.json" ;;
     benchlib:*)
       lib=${step#benchlib:}; tag=$(basename "$lib" .so)
-      MMBA_LIB="$ROOT/$lib" timeout -k 10 400 python -u bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-traffic > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" || { tail "$OUT/bench_$tag.err"; exit 1; }
+      MMBA_LIB="$ROOT/$lib" timeout -k 10 400 python -u bench.py --steps 8 --warmup 3 --full --no-cpu-baseline --no-traffic > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" || { tail "$OUT/bench_$tag.err"; exit 1; }
       cat "$OUT/bench_$tag.json" ;;
     prof)
       cd /tmp && cd "$ROOT"

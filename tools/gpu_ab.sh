@@ -10,7 +10,7 @@ for v in tools/ubench/pcr_probe_v*; do
 done
 timeout -k 10 200 python -u bench.py --path probe=2 --steps 1 --warmup 0 --no-cpu-baseline --no-traffic > "$OUT/k2probe.json" 2> "$OUT/k2probe.err" || { tail "$OUT/k2probe.err"; exit 1; }
 timeout -k 10 300 python -u bench.py --config 1 --steps 8 --warmup 3 --no-cpu-baseline --no-traffic > "$OUT/bench_1.json" 2> "$OUT/bench_1.err" || { tail "$OUT/bench_1.err"; exit 1; }
-timeout -k 10 400 python -u bench.py --config 4 --steps 8 --warmup 3 --no-cpu-baseline > "$OUT/bench_4.json" 2> "$OUT/bench_4.err" || { tail "$OUT/bench_4.err"; exit 1; }
+timeout -k 10 400 python -u bench.py --config 4 --steps 8 --warmup 3 --full --no-cpu-baseline > "$OUT/bench_4.json" 2> "$OUT/bench_4.err" || { tail "$OUT/bench_4.err"; exit 1; }
 grep -h "best\|level" "$OUT"/pcr_probe_v*.txt
 grep "mmba probe" "$OUT/k2probe.err"
 echo done

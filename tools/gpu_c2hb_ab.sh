@@ -6,7 +6,7 @@ mkdir -p $OUT
 for r in 1 2; do
   for v in def PRE_HANDBACK=0 HANDBACK_DMA=1 NE_CF_SPLIT=0; do
     a=; [ $v = def ] || a="--path $v"
-    timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --no-cpu-baseline --no-traffic $a > $OUT/${v}_$r.json 2> $OUT/${v}_$r.err || exit 1
+    timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --full --no-cpu-baseline --no-traffic $a > $OUT/${v}_$r.json 2> $OUT/${v}_$r.err || exit 1
   done
 done
 python3 - $OUT <<'PY'

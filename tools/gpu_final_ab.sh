@@ -3,8 +3,8 @@ set -o pipefail
 OUT=${1:-gpurun_out/fab}
 mkdir -p $OUT
 for r in 1 2; do
-  timeout -k 10 300 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-traffic > $OUT/c4_$r.json 2> $OUT/c4_$r.err || exit 1
-  timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --no-cpu-baseline --no-traffic > $OUT/c1_$r.json 2> $OUT/c1_$r.err || exit 1
+  timeout -k 10 300 python3 bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --no-traffic > $OUT/c4_$r.json 2> $OUT/c4_$r.err || exit 1
+  timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --full --no-cpu-baseline --no-traffic > $OUT/c1_$r.json 2> $OUT/c1_$r.err || exit 1
 done
 python3 - $OUT <<'PY'
 import json, glob, sys

@@ -5,9 +5,9 @@ mkdir -p $OUT
 for r in 1 2 3; do
   for v in def jnt; do
     if [ $v = jnt ]; then export MMBA_LIB=$PWD/tools/ab/libmmba_jnt.so; else unset MMBA_LIB; fi
-    timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --no-cpu-baseline --no-traffic > $OUT/c1_${v}_$r.json 2> $OUT/c1_${v}_$r.err || exit 1
+    timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --full --no-cpu-baseline --no-traffic > $OUT/c1_${v}_$r.json 2> $OUT/c1_${v}_$r.err || exit 1
     if [ $r -le 2 ]; then
-      timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-traffic > $OUT/c4_${v}_$r.json 2> $OUT/c4_${v}_$r.err || exit 1
+      timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-traffic > $OUT/c4_${v}_$r.json 2> $OUT/c4_${v}_$r.err || exit 1
     fi
   done
 done

@@ -4,8 +4,8 @@ OUT=${1:-gpurun_out/kernarg}
 mkdir -p $OUT
 for r in 1 2; do
   for v in 0 1; do
-    HIP_FORCE_DEV_KERNARG=$v timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --no-cpu-baseline --no-traffic > $OUT/c1_k${v}_$r.json 2> $OUT/c1_k${v}_$r.err || exit 1
-    HIP_FORCE_DEV_KERNARG=$v timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-traffic > $OUT/c4_k${v}_$r.json 2> $OUT/c4_k${v}_$r.err || exit 1
+    HIP_FORCE_DEV_KERNARG=$v timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --full --no-cpu-baseline --no-traffic > $OUT/c1_k${v}_$r.json 2> $OUT/c1_k${v}_$r.err || exit 1
+    HIP_FORCE_DEV_KERNARG=$v timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-traffic > $OUT/c4_k${v}_$r.json 2> $OUT/c4_k${v}_$r.err || exit 1
   done
 done
 python3 - $OUT <<'PY'

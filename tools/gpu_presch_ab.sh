@@ -4,7 +4,7 @@ OUT=${1:-gpurun_out/presch}
 mkdir -p $OUT
 for r in 1 2 3; do
   for v in 1 0; do
-    timeout -k 10 300 python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-traffic --path PRE_SCHUR=$v > $OUT/c4_p${v}_$r.json 2> $OUT/c4_p${v}_$r.err || exit 1
+    timeout -k 10 300 python3 bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --no-traffic --path PRE_SCHUR=$v > $OUT/c4_p${v}_$r.json 2> $OUT/c4_p${v}_$r.err || exit 1
   done
 done
 python3 - $OUT <<'PY'

@@ -4,7 +4,7 @@ OUT=${1:-gpurun_out/split2}
 mkdir -p $OUT
 for r in 1 2 3; do
   for v in 1 0; do
-    timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --no-cpu-baseline --no-traffic --path NE_CF_SPLIT=$v > $OUT/s${v}_$r.json 2> $OUT/s${v}_$r.err || exit 1
+    timeout -k 10 300 python3 bench.py --config 1 --steps 12 --warmup 3 --full --no-cpu-baseline --no-traffic --path NE_CF_SPLIT=$v > $OUT/s${v}_$r.json 2> $OUT/s${v}_$r.err || exit 1
   done
 done
 python3 - $OUT <<'PY'
