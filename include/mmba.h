@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MMBA_ABI_VERSION 10
+#define MMBA_ABI_VERSION 11
 
 /* Return codes. */
 #define MMBA_OK 0
@@ -634,7 +634,13 @@ typedef struct mmba_kernel_stats {
                                lists the speculative hand-back stored (one
                                kernel behind the trial the device decided
                                ends the solve)                            */
-    int32_t reserved10;
+    int32_t ne_split_launches; /* ABI 11 (the reserved slot of ABI 10): launches
+                               of the four-workgroups-per-camera-frame normal
+                               equation kernel (k_ne_cf_split, the long-segment
+                               C2 route) on this plan since it was created; 0
+                               where the route is not taken or pinned off
+                               (MMBA_PATH_NE_CF_SPLIT = 0); a group plan
+                               reports its first shard's                   */
 } mmba_kernel_stats;
 int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                            mmba_kernel_stats *out);

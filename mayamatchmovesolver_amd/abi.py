@@ -22,7 +22,7 @@ AUTO_DIFF_TYPE_CENTRAL = 1
 ROBUST_LOSS_TYPE_TRIVIAL = 0
 ROBUST_LOSS_TYPE_SOFT_L_ONE = 1
 ROBUST_LOSS_TYPE_CAUCHY = 2
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # mmba_debug_set_path keys (test hook: pin a plan-builder choice)
 PATH_PCR = 1
@@ -238,7 +238,7 @@ class MmbaKernelStats(C.Structure):
         ("band_block", C.c_int32),
         ("chol_flops_alg", C.c_double),
         ("pre_handbacks", C.c_int32),
-        ("reserved10", C.c_int32),
+        ("ne_split_launches", C.c_int32),
     ]
 
     def as_dict(self):

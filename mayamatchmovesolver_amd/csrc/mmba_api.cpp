@@ -425,6 +425,7 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing, mmba_kernel_stats
         out->shards_replicated = p.replicated ? 1 : 0;
         out->spec_replays = p.spec_replays;
         out->pre_handbacks = (int32_t)p.pre_handbacks;
+        out->ne_split_launches = (int32_t)p.ne_split_launches;
         {
             const BandSolver &b = p.bs;
             out->band_solver = !p.band ? 0

@@ -215,7 +215,9 @@ void launch_jac_ne(hipStream_t s, const DevProblem &P, const double *recs, const
 // Whether launch_ne can fuse the bookkeeping (uniform camera blocks, fast
 // bundles, no global parameters).
 bool ne_epilogue_fusable(const DevProblem &P);
-void launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
+// Returns whether the camera-frame pass was k_ne_cf_split (counted by the
+// plan: mmba_kernel_stats.ne_split_launches).
+bool launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
                const int *nloc, const double *f, double *Acc, double *Acg, double *Abb,
                double *Abg, double *aggbuf, double *g, double *glob_partial, int glob_chunk,
                const NeEpi &epi = NeEpi(), bool cf_done = false);

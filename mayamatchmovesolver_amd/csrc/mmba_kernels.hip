@@ -1365,9 +1365,12 @@ __device__ __forceinline__ void ne_cf_u_body(const DevProblem &P, const double *
 // camera-frame (logical blocks cf * NS + part, consecutive on one XCD), part
 // p takes observations o0 + 64 NW p + t, o0 + 64 NW (NS + p) + t, ...; each
 // workgroup stores its NT partial sums write-through, the last to arrive
-// (per camera-frame ticket: monotonic, last when old % NS == NS - 1) loads
-// them sc1 and adds them in part order -- deterministic whichever arrives
-// last -- then writes Acc / g and the lmder epilogue as k_ne_cf_u does.
+// (per camera-frame ticket: monotonic, last when old % NS == NS - 1; the
+// increment releases the workgroup's partials and the last arriver acquires
+// its peers', as k_reduce_multi does) loads them sc1 and adds them in part
+// order -- deterministic whichever arrives last, solve after solve on one
+// plan (tests/test_gpu_long_segments.py) -- then writes Acc / g and the lmder
+// epilogue as k_ne_cf_u does.
 template <int PC, int NW, int NS>
 __global__ void __launch_bounds__(64 * NW) k_ne_cf_split(DevProblem P, const double *__restrict__ J,
                                                          const double *__restrict__ f, double *Acc,
@@ -1425,11 +1428,13 @@ __global__ void __launch_bounds__(64 * NW) k_ne_cf_split(DevProblem P, const dou
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0)
-        last_s = (__hip_atomic_fetch_add(&E.cf_ticket[cf], 1u, __ATOMIC_RELAXED,
+        last_s = (__hip_atomic_fetch_add(&E.cf_ticket[cf], 1u, __ATOMIC_ACQ_REL,
                                          __HIP_MEMORY_SCOPE_AGENT) %
                   NS) == NS - 1;
     __syncthreads();
     if (!last_s) return;
+    // the peers' partial sums, released by their ticket increments
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const double *all = E.cf_part + (size_t)cf * NS * NE_CF_NT;
     for (int e = tid; e < NT; e += 64 * NW) {
         double t[NS];  // every part's load issued before the sum
@@ -4324,13 +4329,14 @@ bool ne_epilogue_fusable(const DevProblem &P) {
     return P.nG == 0 && (P.JB || P.nbs == 0) && (P.pc_uniform == 6 || P.pc_uniform == 7) &&
            !P.rs;
 }
-void launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
+bool launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
                const int *nloc, const double *f, double *Acc, double *Acg, double *Abb,
                double *Abg, double *aggbuf, double *g, double *glob_partial, int glob_chunk,
                const NeEpi &epi, bool cf_done) {
     const NeEpi E = ne_epilogue_fusable(P) ? epi : NeEpi();
     double *Agg = aggbuf, *gG = aggbuf + NGMAX * NGMAX;
     bool glob_done = false;  // the global chunks ran in the camera-frame launch
+    bool split_done = false;  // the camera-frame pass was k_ne_cf_split
     if (P.rs) {  // coupled camera-frame blocks (mmba_rs.hip)
         launch_ne_rs(s, P, J, jcol, nloc, f, Acc, Acg, g);
     } else if (P.ncf > 0 && !cf_done) {
@@ -4354,6 +4360,7 @@ void launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *j
             if (P.nG == 0) {
                 const bool split = wide && E.cf_part && E.cf_ticket && P.M > 1024 * P.ncf;
                 if (split) {  // long segments: NE_CF_SPLIT workgroups per camera-frame
+                    split_done = true;
                     const int gs = P.ncf * NE_CF_SPLIT;
                     if (pcu == 6)
                         k_ne_cf_split<6, 4, NE_CF_SPLIT><<<gs, 256, 0, s>>>(P, J, f, Acc, g, E);
@@ -4398,6 +4405,7 @@ void launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *j
             k_ne_glob_wide<<<nb, 256, 0, s>>>(P, J, jcol, nloc, f, glob_partial, glob_chunk);
         k_ne_glob_reduce<<<1, 256, 0, s>>>(P, glob_partial, nb, Agg, gG);
     }
+    return split_done;
 }
 void launch_colnorms(hipStream_t s, const DevProblem &P, const double *Acc, const double *Abb,
                      const double *aggbuf, double *acnorm, double *g) {

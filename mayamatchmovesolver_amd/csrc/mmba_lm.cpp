@@ -478,9 +478,10 @@ void Plan::jac(const double *dx, const JacLM *lm) {
     launch_rows_jac(s, P, d_ext, d_ext_pert, d_step, central ? d_ext_pertB : nullptr,
                     central ? d_stepB : nullptr, lmder ? 1 : 0, d_Jrow, d_eu + 2 * (size_t)M,
                     n - 1);
-    if (!pre_bnd)
+    if (!pre_bnd &&
         launch_ne(s, P, d_J, d_jcol, d_nloc, d_f, d_Acc, d_Acg, d_Abb, d_Abg, d_Agg, d_g,
-                  d_glob_partial, glob_chunk, epi, k2_fused);
+                  d_glob_partial, glob_chunk, epi, k2_fused))
+        ++ne_split_launches;
     launch_rows_ne(s, P, d_Jrow, d_f + 2 * (size_t)M, d_p_own, d_Acc, d_Abb, d_Agg, d_g);
     if (nG > 0) allreduce(d_Agg, NGMAX * NGMAX + NGMAX);  // global block: all shards
     if (fuse) {

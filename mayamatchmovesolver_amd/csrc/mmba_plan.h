@@ -597,6 +597,7 @@ struct Plan {
     // that trial and the device's slots say the kernel stored them
     bool pre_hb_on = false, pre_hb_enq = false;
     long long pre_handbacks = 0;  // solves whose lists the speculative hand-back stored
+    long long ne_split_launches = 0;  // k_ne_cf_split launches (launch_ne took the split branch)
     double *pre_hb_map[3] = {nullptr, nullptr, nullptr};
 };
 

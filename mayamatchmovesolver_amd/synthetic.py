@@ -320,7 +320,8 @@ def make_config(index: int, frames: int | None = None, scale: float = 1.0,
                 scene_graph_mode=abi.SCENE_GRAPH_MODE_MM_SCENE_GRAPH, window: int = 4,
                 depth=(20.0, 200.0), lens_model: str = "classic",
                 init_noise: float = 1.0, obs_noise: float = 1.0,
-                rolling_shutter: float = 0.0, cameras: int = 2) -> Problem:
+                rolling_shutter: float = 0.0, cameras: int = 2,
+                solve_focal: bool = True) -> Problem:
     """Concrete synthetic input for BASELINE.json ``configs[index]``.
 
     ``frames`` / ``scale`` shrink a configuration (frame-window subsets and
@@ -348,12 +349,15 @@ def make_config(index: int, frames: int | None = None, scale: float = 1.0,
     ``cameras`` (configs[4] only): cameras sharing the lens (the spec's 2; 1
     gives the one-camera shot whose animated lens coefficients each reach one
     camera-frame).
+    ``solve_focal`` (configs[1] only): False locks the focal length at its
+    initial guess, leaving the six pose parameters per frame (the spec solves
+    pose + focal: seven); the scene's random draws are the same either way.
     """
     rng = np.random.Generator(np.random.PCG64(20241008 + index))
     if index == 0:
         return _config_c1(rng, frames or 10)
     if index == 1:
-        return _config_c2(rng, frames or 120, scale)
+        return _config_c2(rng, frames or 120, scale, solve_focal)
     if index == 2:
         return _config_ba(rng, index, n_cams=10, F=frames or 500, B=int(10000 * scale),
                           K=int(50000 * scale), window=20, per_cam_markers=True,
@@ -579,9 +583,10 @@ def _blend_at(v, fs, tau):
     return (cv + tau * b) + (tau * tau) * c
 
 
-def _config_c2(rng, F, scale):
+def _config_c2(rng, F, scale, solve_focal=True):
     """1 camera, 1k locked bundles, 5k markers (k -> k mod 1000), windows U[20,60];
-    solve camera translate/rotate + focal per frame."""
+    solve camera translate/rotate + focal per frame (``solve_focal`` False: the
+    focal length stays locked at its initial guess)."""
     B, K = max(1, int(1000 * scale)), max(1, int(5000 * scale))
     t, r = _camera_path(rng, F, 0)
     focal = FOCAL_MM * (1.0 + 0.05 * np.sin(0.02 * np.arange(F)))
@@ -594,7 +599,8 @@ def _config_c2(rng, F, scale):
     r0 = r + rng.uniform(-2.0, 2.0, size=r.shape)
     f0 = focal * (1.0 + rng.uniform(-0.05, 0.05, size=F))
     return _bulk_problem(F, [t0], [r0], [f0],
-                         lambda tids, cids: list(tids[:6]) + [cids[abi.CAM_FOCAL_MM]],
+                         lambda tids, cids: list(tids[:6]) +
+                         ([cids[abi.CAM_FOCAL_MM]] if solve_focal else []),
                          P, np.zeros(B, bool), np.zeros(K, np.int32), mkr_bnd, ks, fs, xy,
                          meta={"name": CONFIG_NAMES[1]})
 

@@ -20,11 +20,14 @@ def rel_err(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300))) if a.size else 0.0
 
 
-def check_solve(prob, opt, oracle, gpu_ctx, x_tol=REL, trace_tol=REL):
+def check_solve(prob, opt, oracle, gpu_ctx, x_tol=REL, trace_tol=REL, run=None):
+    """``run`` (optional): callable(solver) -> SolveResult in place of a plain
+    ``solve()``, for a caller that passes its own output buffers or reads the
+    plan's kernel statistics before the plan is closed."""
     xr, fr, eur, edr, rr, trr = oracle.solve(prob, opt)
     s = Solver(prob, opt, context=gpu_ctx)
     try:
-        out = s.solve()
+        out = run(s) if run is not None else s.solve()
     finally:
         s.close()
     g = out.result
