@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MMBA_ABI_VERSION 11
+#define MMBA_ABI_VERSION 12
 
 /* Return codes. */
 #define MMBA_OK 0
@@ -744,6 +744,19 @@ int mmba_debug_dgemm(mmba_context *ctx, int tri, int in_place, int M, int N, int
  * ||S xR - r|| / ||r|| -- the full-size dense solve's own accuracy.
  * MMBA_ERR_UNSUPPORTED for other plans. */
 int mmba_debug_reduced_residual(mmba_plan *plan, const double *x, double lam, double *relres);
+
+/* Test hook (not part of the solver seam; ABI 12): the linear algebra of one
+ * LM iteration at internal x, as a solve's first iteration runs it --
+ * evaluation, Jacobian pass with MINPACK's first-call scaling D = ||J col||
+ * (1 for a zero column), normal equations, then the damped solve
+ * (J^T J + lam D^2) p = J^T f through the plan's own Schur complement, reduced
+ * solver and back substitution.  Outputs (each may be NULL), in parameter
+ * order: step_out [n] = p, g_out [n] = J^T f, diag_out [n] = D, and fjac_out
+ * [m x n, column-major] = the dense J reassembled after the solve from what
+ * the pass stored.  MMBA_ERR_INVALID when the factorisation fails;
+ * MMBA_ERR_UNSUPPORTED for sharded, multi-device and B15 plans. */
+int mmba_debug_damped_step(mmba_plan *plan, const double *x, double lam, double *step_out,
+                           double *g_out, double *diag_out, double *fjac_out);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ AUTO_DIFF_TYPE_CENTRAL = 1
 ROBUST_LOSS_TYPE_TRIVIAL = 0
 ROBUST_LOSS_TYPE_SOFT_L_ONE = 1
 ROBUST_LOSS_TYPE_CAUCHY = 2
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # mmba_debug_set_path keys (test hook: pin a plan-builder choice)
 PATH_PCR = 1
@@ -258,6 +258,7 @@ EXPORTED_SYMBOLS = [
     "mmba_context_create_multi",
     "mmba_context_num_devices",
     "mmba_plan_num_shards",
+    "mmba_debug_damped_step",
     "mmba_debug_reduced_residual",
     "mmba_context_destroy",
     "mmba_context_synchronize",

@@ -527,6 +527,21 @@ int mmba_debug_reduced_residual(mmba_plan *plan, const double *x, double lam, do
     })
 }
 
+int mmba_debug_damped_step(mmba_plan *plan, const double *x, double lam, double *step_out,
+                           double *g_out, double *diag_out, double *fjac_out) {
+    if (!plan || !x || !(lam >= 0.)) return MMBA_ERR_INVALID;
+    if (plan->group) {
+        set_error("unsupported: damped step hook on a multi-device plan");
+        return MMBA_ERR_UNSUPPORTED;
+    }
+    MMBA_GUARD({
+        Plan &p = plan->impl;
+        MMBA_HIP(hipSetDevice(p.ctx->device));
+        p.outputs_ready = false;
+        return p.damped_step(x, lam, step_out, g_out, diag_out, fjac_out);
+    })
+}
+
 int mmba_debug_dgemm(mmba_context *ctx, int tri, int in_place, int M, int N, int K,
                      const double *A, int lda, const double *B, int ldb, double *C, int ldc,
                      double alpha, double beta) {

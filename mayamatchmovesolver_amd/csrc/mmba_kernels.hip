@@ -4371,12 +4371,8 @@ bool launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *j
                 } else {
                     if (wide) MMBA_NE_U(7, 4, 0); else MMBA_NE_U(7, 1, 0);
                 }
-            } else {
-                if (pcu == 6) {
-                    if (wide) MMBA_NE_U(6, 4, 2); else MMBA_NE_U(6, 1, 2);
-                } else {
-                    if (wide) MMBA_NE_U(7, 4, 2); else MMBA_NE_U(7, 1, 2);
-                }
+            } else {  // one or two globals on short segments (wide: k_ne_cf_glob above)
+                if (pcu == 6) MMBA_NE_U(6, 1, 2); else MMBA_NE_U(7, 1, 2);
             }
         } else {
             k_ne_cf<<<P.ncf, 256, 0, s>>>(P, J, jcol, nloc, f, Acc, Acg, g);

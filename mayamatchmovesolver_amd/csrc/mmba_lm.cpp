@@ -1311,6 +1311,13 @@ int Plan::dense_jacobian(const double *x, double *fjac) {
     P.jcol_implicit = 0;  // this host-side reassembly reads jcol
     jac(d_x);
     P.jcol_implicit = implicit;
+    assemble_dense_jacobian(fjac);
+    return MMBA_OK;
+}
+
+// The dense reference-order Jacobian (column-major, ldfjac = m) from what the
+// last Jacobian pass stored: d_J / d_jcol / d_nloc and the attribute rows.
+void Plan::assemble_dense_jacobian(double *fjac) {
     std::vector<double> J((size_t)2 * P.lmax * M), Jr(nrows);
     std::vector<int> jc((size_t)std::max(P.lmax, 1) * M), nl(M), rp(nrows);
     if (nrows > 0) {
@@ -1349,7 +1356,6 @@ int Plan::dense_jacobian(const double *x, double *fjac) {
             }
         }
     }
-    return MMBA_OK;
 }
 
 // ||S x - r||^2 and ||r||^2 of a dense symmetric S (lower triangle,
@@ -1403,6 +1409,57 @@ int Plan::reduced_residual(const double *x, double lam, double *relres) {
     if (h_scalar[SL_FAIL] != 0.) throw Invalid{"reduced residual hook: the factorisation failed"};
     *relres = std::sqrt(h[0] / h[1]);
     collect_spans();
+    return MMBA_OK;
+}
+
+// Test hook (mmba_debug_damped_step): one LM iteration's linear algebra at x
+// as a solve's first iteration runs it -- evaluation, Jacobian pass with the
+// lmder bookkeeping (first = 1, mode = 1: D = column norms), damped solve --
+// then the step, g, D and the dense J the pass stored, in parameter order.
+int Plan::damped_step(const double *x, double lam, double *step_out, double *g_out,
+                      double *diag_out, double *fjac_out) {
+    if (nranks > 1) throw Unsupported{"damped step hook: sharded plan"};
+    if (b15) throw Unsupported{"damped step hook: B15 plan"};
+    if (fjac_out && P.jcol_implicit && !dbg_jcol_stored) {
+        // uniform fast plans store no jcol (a property of the plan): one
+        // Jacobian pass with it stored, ahead of the pass under test
+        pend_red = false;
+        attrs_reset();
+        MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        fun(d_x, d_f, d_eu, d_ed);
+        P.jcol_implicit = 0;
+        try {
+            jac(d_x);
+        } catch (...) {
+            P.jcol_implicit = 1;
+            throw;
+        }
+        P.jcol_implicit = 1;
+        dbg_jcol_stored = true;
+    }
+    // an epilogue reduction a previous entry point deferred (pend_red) reads
+    // d_partial rows this call rewrites: dropped, its slots are not read
+    // outside the solve that deferred it
+    pend_red = false;
+    attrs_reset();
+    MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
+    MMBA_HIP(hipMemsetAsync(d_diag, 0, sizeof(double) * n, s));
+    fun(d_x, d_f, d_eu, d_ed);
+    const JacLM lm{1, 1, 1.0, nullptr};
+    jac(d_x, &lm);
+    solve_damped_enqueue(lam, SL_DNORM);
+    read_slots(SL_DNORM, SL_FAIL);
+    if (h_scalar[SL_FAIL] != 0.) throw Invalid{"damped step hook: the factorisation failed"};
+    if (step_out)
+        MMBA_HIP(hipMemcpyAsync(step_out, d_xs, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (g_out) MMBA_HIP(hipMemcpyAsync(g_out, d_g, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    if (diag_out)
+        MMBA_HIP(hipMemcpyAsync(diag_out, d_diag, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    host_sync();
+    if (fjac_out)
+        assemble_dense_jacobian(fjac_out);  // after the solve: what the pass itself stored
+    else
+        collect_spans();
     return MMBA_OK;
 }
 

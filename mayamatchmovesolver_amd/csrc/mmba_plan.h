@@ -569,6 +569,12 @@ struct Plan {
     bool dbg_keep_S = false;
     double *d_Skeep = nullptr, *d_rkeep = nullptr;
     int reduced_residual(const double *x, double lam, double *relres);
+    // test hook (mmba_debug_damped_step): the damped step of one LM iteration
+    // at x, with g, D and the dense J its Jacobian pass stored
+    bool dbg_jcol_stored = false;  // d_jcol filled for a plan that leaves it implicit
+    void assemble_dense_jacobian(double *fjac);
+    int damped_step(const double *x, double lam, double *step_out, double *g_out,
+                    double *diag_out, double *fjac_out);
     int reproject(const double *x, double *point_out, double *marker_out);
     int measure(const double *x, double *fvec_out, double *eu_out, double *ed_out,
                 double *stats);

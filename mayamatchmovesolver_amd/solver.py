@@ -267,6 +267,21 @@ class Solver:
         check(lib().mmba_debug_reduced_residual(self._h, _dp(xx), float(lam), _dp(out)))
         return float(out[0])
 
+    def damped_step(self, x=None, lam: float = 0.0, jacobian: bool = True):
+        """One LM iteration's linear algebra at x (test hook
+        ``mmba_debug_damped_step``): the damped step p of
+        (J^T J + lam D^2) p = J^T f as the plan's kernels solve it, with
+        g = J^T f, D (MINPACK's first-call scaling) and the dense J (m x n) the
+        Jacobian pass stored (None with ``jacobian=False``)."""
+        p = self.problem
+        m, n = p.num_residuals, p.num_params
+        xx = np.ascontiguousarray(p.x0 if x is None else x, dtype=np.float64)
+        step, g, diag = np.zeros(n), np.zeros(n), np.zeros(n)
+        fjac = np.zeros(m * n) if jacobian else None
+        check(lib().mmba_debug_damped_step(self._h, _dp(xx), float(lam), _dp(step), _dp(g),
+                                           _dp(diag), _dp(fjac)))
+        return step, g, diag, (fjac.reshape(n, m).T if jacobian else None)
+
     def set_timing(self, enable=True):
         st = abi.MmbaKernelStats()
         self._timing = bool(enable)

@@ -321,7 +321,7 @@ def make_config(index: int, frames: int | None = None, scale: float = 1.0,
                 depth=(20.0, 200.0), lens_model: str = "classic",
                 init_noise: float = 1.0, obs_noise: float = 1.0,
                 rolling_shutter: float = 0.0, cameras: int = 2,
-                solve_focal: bool = True) -> Problem:
+                solve_focal: bool = True, block_focal: bool = False) -> Problem:
     """Concrete synthetic input for BASELINE.json ``configs[index]``.
 
     ``frames`` / ``scale`` shrink a configuration (frame-window subsets and
@@ -352,6 +352,9 @@ def make_config(index: int, frames: int | None = None, scale: float = 1.0,
     ``solve_focal`` (configs[1] only): False locks the focal length at its
     initial guess, leaving the six pose parameters per frame (the spec solves
     pose + focal: seven); the scene's random draws are the same either way.
+    ``block_focal`` (configs[4] only): True keys the focal length per frame and
+    solves it with the pose -- seven parameters per camera-frame beside the
+    shared lens' two global coefficients (the spec's focal length is locked).
     """
     rng = np.random.Generator(np.random.PCG64(20241008 + index))
     if index == 0:
@@ -367,7 +370,8 @@ def make_config(index: int, frames: int | None = None, scale: float = 1.0,
                           K=int(50000 * scale), window=window, per_cam_markers=False,
                           depth=depth, init_noise=init_noise, obs_noise=obs_noise)
     if index == 4:
-        return _config_c5(rng, frames or 240, scale, lens_model, rolling_shutter, cameras)
+        return _config_c5(rng, frames or 240, scale, lens_model, rolling_shutter, cameras,
+                          block_focal)
     raise KeyError(index)
 
 
@@ -687,7 +691,8 @@ def _config_ba(rng, index, n_cams, F, B, K, window, per_cam_markers, depth=(20.0
                          meta={"name": CONFIG_NAMES[index]})
 
 
-def _config_c5(rng, F, scale, lens_model="classic", rolling_shutter=0.0, n_cams=2):
+def _config_c5(rng, F, scale, lens_model="classic", rolling_shutter=0.0, n_cams=2,
+               block_focal=False):
     """2 cams, 1k locked bundles, 2k markers (1k per cam), windows mean 60,
     one shared 3DE-classic lens with distortion + quartic solved (lens attrs first).
     ``rolling_shutter`` = rs (frames, time shift x fps) != 0: both cameras
@@ -765,7 +770,7 @@ def _config_c5(rng, F, scale, lens_model="classic", rolling_shutter=0.0, n_cams=
     ks, fs, xy = _obs_from_windows(rng, start, length, proj)
     t0 = [tc + rng.uniform(-0.05, 0.05, size=tc.shape) for tc in ts]
     r0 = [rc + rng.uniform(-2.0, 2.0, size=rc.shape) for rc in rs]
-    wide = lens_model == "classic_wide"
+    wide = lens_model == "classic_wide" or block_focal
     focal0 = [FOCAL_MM * (1.0 + rng.uniform(-0.01, 0.01, F)) if wide else FOCAL_MM
               for _ in range(n_cams)]
     offset0 = None
