@@ -692,8 +692,10 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                                       but 4.5e-6 off the oracle's one-step ||f|| on the
                                       160-frame C4-spec scene where Cholesky is 1.8e-8 off);
                                       2 LDL^T with 1 x 1 pivots */
-#define MMBA_PATH_BACKSUB_ONEPASS 17 /* 1: the trial back substitution forms u_i = W_i^T x
-                                         itself (no k_obs_wtx launch; same sums) */
+#define MMBA_PATH_BACKSUB_ONEPASS 17 /* 1 / 0: the trial back substitution forms u_i = W_i^T x
+                                         itself (no k_obs_wtx launch; same sums) / reads them
+                                         from k_obs_wtx; default: itself in the group form
+                                         (MMBA_PATH_BACKSUB_GROUP), k_obs_wtx otherwise */
 #define MMBA_PATH_JB_RECOMPUTE 18  /* 1: the bundle pass re-evaluates each observation's bundle
                                       columns instead of reading the 64-B records the fused
                                       Jacobian pass stores (same bits; measured slower on C4) */
@@ -709,7 +711,11 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                                       launch of it behind each decided trial */
 #define MMBA_PATH_PRE_SCHUR 23     /* 1: the next damped solve's k_schur_obs is enqueued with the
                                       gated Jacobian ahead of the host's decision */
-#define MMBA_PATH_NUM 24
+#define MMBA_PATH_BACKSUB_GROUP 24 /* trial back substitution: 1 a group of four lanes per bundle
+                                      (a lane per observation of each chunk of four, a lane per
+                                      parameter; same sums), 0 one thread per bundle; default:
+                                      the group form, except on rolling-shutter plans */
+#define MMBA_PATH_NUM 25
 int mmba_debug_set_path(int key, int value);
 
 /* Test hook (not part of the solver seam): solve S x = r with the device

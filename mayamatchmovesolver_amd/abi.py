@@ -48,7 +48,8 @@ PATH_RED_BD = 20
 PATH_HANDBACK_DMA = 21
 PATH_PRE_HANDBACK = 22
 PATH_PRE_SCHUR = 23
-PATH_NUM = 24
+PATH_BACKSUB_GROUP = 24
+PATH_NUM = 25
 
 FILM_FIT_FILL = 0
 FILM_FIT_HORIZONTAL = 1

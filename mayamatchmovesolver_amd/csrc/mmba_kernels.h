@@ -301,6 +301,16 @@ struct TrialFold {
     // launched; the other parameters are then exactly the camera-frames'
     int rec = 0;
     double *recs = nullptr, *brec = nullptr;
+    // group (MMBA_PATH_BACKSUB_GROUP): four lanes per bundle -- a lane per
+    // observation of each chunk of four, a lane per parameter (the sums in
+    // the thread-per-bundle order, values passed by shuffle).  bobs_rp[q] =
+    // {cf_roff, cf_pc} of the camera-frame of observation bobs[q] (the
+    // one-pass form's x_cf rows without the obs_cf -> cf_pc / cf_roff steps).
+    // brec_fwd (Plan::brec_fwd): the bundle records come from the lanes'
+    // registers instead of the attribute block they just stored to.
+    int group = 0;
+    const int2 *bobs_rp = nullptr;
+    int brec_fwd = 0;
 };
 // Whether the trial's records can be built inside the back substitution: no
 // global parameter (every non-bundle parameter belongs to one camera-frame),

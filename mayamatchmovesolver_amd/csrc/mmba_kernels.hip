@@ -3276,6 +3276,288 @@ __global__ void __launch_bounds__(64) k_backsub_trial(DevProblem P, const double
     }
 }
 
+// k_backsub_trial with a group of four lanes per bundle (256 threads over the
+// same 64 bundles per workgroup; MMBA_PATH_BACKSUB_GROUP).  Lane k of a group
+// owns observation qb + k of each chunk of four and, for k < pb, parameter k.
+// Loads come in three dependent levels, all issued before the first store: by
+// bundle; by the lane's parameter and observation slot; the U record (or the
+// W row and x_cf, ONEPASS) and the record's undriven components.  Every sum
+// keeps the thread-per-bundle order: the u_i are subtracted in observation
+// order from values passed by shuffle (all four lanes hold the same s and
+// solve the same 3 x 3 system), pn / xn are added over a = 0, 1, 2 and enter
+// the same 64-leaf tree.  No shuffle sits under a branch that depends on the
+// lane within its group.  W18: wst == 18 (pc_uniform 6), the W row as nine
+// 16-B loads.  The camera-frame-record and T.other workgroups work on their
+// first 64 lanes as in k_backsub_trial.
+template <bool ONEPASS, bool W18>
+__global__ void __launch_bounds__(256) k_backsub_trial_g(DevProblem P, const double *__restrict__ U,
+                                                         const double *__restrict__ W,
+                                                         const double *__restrict__ Wg,
+                                                         const double *__restrict__ tb,
+                                                         const double *__restrict__ Lb,
+                                                         const double *__restrict__ xR, double *x,
+                                                         int nbb, int nob, TrialFold T) {
+    __shared__ double red[128];
+    const int tid = threadIdx.x;
+    // physical blocks [0, nob): the camera-frame-record / T.other workgroups
+    // (the longer chain: dispatched first), [nob, pad) idle, [pad, pad + nbb) the
+    // bundle workgroups -- pad a multiple of 8, so bundle block bb still runs on
+    // XCD bb mod 8; lb = the workgroup's index in k_backsub_trial's grid
+    const int pad = (nob + 7) & ~7;
+    if ((int)blockIdx.x >= nob && (int)blockIdx.x < pad) return;
+    const int bb = (int)blockIdx.x - pad, ob = (int)blockIdx.x;
+    const int lb = bb >= 0 ? bb : nbb + ob;
+    double pn = 0., xn = 0.;
+    int leaf = tid < 64 ? tid : -1;  // this lane's leaf of the workgroup's tree
+    if (bb >= 0) {
+        const int k = tid & 3;
+        const int b = xcd_remap(bb, nbb) * 64 + (tid >> 2);
+        const bool live = b < P.nB;
+        const bool fwd = T.rec && T.brec_fwd && P.bnd_vx;  // records from registers
+        leaf = k == 0 ? (tid >> 2) : -1;
+        // level 1: by bundle
+        int pb = 0, q0 = 0, q1 = 0, pcm = 0;
+        int4 p4 = make_int4(-1, -1, -1, -1), vx = make_int4(-1, -1, -1, 0);
+        double s[3] = {0., 0., 0.};
+        double L[3][3] = {};
+        if (live) {
+            pb = P.bnd_pb[b];
+            p4 = P.bnd_p4[b];
+            q0 = P.bobs_off[b];
+            q1 = P.bobs_off[b + 1];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) s[a] = tb[(size_t)b * 3 + a];
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) L[a][c] = Lb[(size_t)b * 9 + a * 3 + c];
+            if (fwd) {
+                vx = P.bnd_vx[b];
+                pcm = P.bnd_pcomp[b];
+            }
+        }
+        if (pb == 0) q1 = q0;  // no solved parameter: the record only
+        // level 2: by the lane's parameter
+        const int j = k < pb ? (k == 0 ? p4.x : (k == 1 ? p4.y : p4.z)) : -1;
+        double dg = 0., x0 = 0., xmin = 0., xmax = 0., off = 0., sc = 1.;
+        long long vi = 0;
+        bool own = false;
+        if (j >= 0) {
+            dg = T.diag[j];
+            x0 = T.x[j];
+            xmin = P.p_min[j];
+            xmax = P.p_max[j];
+            off = P.p_off[j];
+            sc = P.p_scale[j];
+            vi = P.p_vidx[j];
+            own = own_mask(T.own, j);
+        }
+        // level 2: by the lane's observation slot
+        int i = -1;
+        int2 rp = make_int2(0, 0);
+        if (q0 + k < q1) {
+            i = P.bobs[q0 + k];
+            if (ONEPASS) rp = T.bobs_rp[q0 + k];
+        }
+        // the record's components that no parameter of the bundle drives
+        const int pw = fwd ? p4.w : -1;
+        double base[3] = {0., 0., 0.};
+        if (pw >= 0) {
+            int dm = 0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+                if (a < pw) dm |= 1 << ((pcm >> (2 * a)) & 3);
+            if (vx.x >= 0 && !(dm & 1)) base[0] = P.attr_val[vx.x];
+            if (vx.y >= 0 && !(dm & 2)) base[1] = P.attr_val[vx.y];
+            if (vx.z >= 0 && !(dm & 4)) base[2] = P.attr_val[vx.z];
+        }
+        const double4 *U4 = reinterpret_cast<const double4 *>(U);
+        for (int qb = q0; qb < q1; qb += 4) {
+            // level 3: the lane's u_i
+            double u[3] = {0., 0., 0.};
+            if (i >= 0) {
+                if (ONEPASS && W18) {
+                    const double2 *row = reinterpret_cast<const double2 *>(&W[(size_t)i * 18]);
+                    double2 r2[9];
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) r2[t] = row[t];
+                    const int pc = min(rp.y, 6);
+                    double xv[6];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) xv[a] = a < pc ? xR[rp.x + a] : 0.;
+                    double w[18];
+#pragma unroll
+                    for (int t = 0; t < 9; ++t) {
+                        w[2 * t] = r2[t].x;
+                        w[2 * t + 1] = r2[t].y;
+                    }
+#pragma unroll
+                    for (int a = 0; a < 6; ++a)
+                        if (a < pc) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) u[c] += w[a * 3 + c] * xv[a];
+                        }
+                } else if (ONEPASS) {
+                    const int pc = min(rp.y, P.wst / 3);
+                    const double *row = &W[widx(P, 0, i)];
+                    for (int a = 0; a < pc; ++a) {
+                        const double xv = xR[rp.x + a];
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) u[c] += row[a * 3 + c] * xv;
+                    }
+                } else {
+                    const double4 uu = U4[i];
+                    u[0] = uu.x;
+                    u[1] = uu.y;
+                    u[2] = uu.z;
+                }
+            }
+            // the next chunk's slot
+            i = -1;
+            if (qb + 4 + k < q1) {
+                i = P.bobs[qb + 4 + k];
+                if (ONEPASS) rp = T.bobs_rp[qb + 4 + k];
+            }
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const double a0 = __shfl(u[0], kk, 4), a1 = __shfl(u[1], kk, 4),
+                             a2 = __shfl(u[2], kk, 4);
+                if (qb + kk < q1) {
+                    s[0] -= a0;
+                    s[1] -= a1;
+                    s[2] -= a2;
+                }
+            }
+        }
+        double xb[3] = {0., 0., 0.};
+        if (pb > 0) {
+            const int nG = P.nG;
+            const int nCF = P.nR - nG;
+            for (int q = 0; q < nG; ++q) {
+                const double xv = xR[nCF + q];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s[c] -= Wg[((size_t)b * NGMAX + q) * 3 + c] * xv;
+            }
+#pragma unroll
+            for (int a = 2; a >= 0; --a) {
+                if (a >= pb) continue;
+                double t = s[a];
+#pragma unroll
+                for (int kk = a + 1; kk < 3; ++kk)
+                    if (kk < pb) t -= L[kk][a] * xb[kk];
+                xb[a] = t / L[a][a];
+            }
+        }
+        // the lane's parameter: trial_one_pre's operations from the loaded operands
+        double e = 0., ep = 0., stp = 0., pl = 0., xl = 0.;
+        if (j >= 0) {
+            const double xs = k == 0 ? xb[0] : (k == 1 ? xb[1] : xb[2]);
+            x[j] = xs;
+            const double st = -xs;
+            const double xj = x0 + st;
+            const double w3 = dg * st;
+            T.wa1[j] = st;
+            T.wa2[j] = xj;
+            T.wa3[j] = w3;
+            e = int_to_ext(xj, xmin, xmax, off, sc);
+            T.ext[j] = e;
+            const double xp = fd_point(xj, xmin, xmax, T.solver_type, T.delta, T.eps_dif, stp);
+            T.step[j] = stp;
+            ep = int_to_ext(xp, xmin, xmax, off, sc);
+            T.ext_pert[j] = ep;
+            P.attr_val[vi] = e;
+            if (own) {  // sharded: each parameter counted by its owner
+                pl = w3 * w3;
+                const double v = dg * xj;
+                xl = v * v;
+            }
+        }
+        // the bundle's sums over a = 0, 1, 2 in that order (0 where not counted)
+        pn = (__shfl(pl, 0, 4) + __shfl(pl, 1, 4)) + __shfl(pl, 2, 4);
+        xn = (__shfl(xl, 0, 4) + __shfl(xl, 1, 4)) + __shfl(xl, 2, 4);
+        if (T.rec) {
+            if (fwd) {
+                // the bundle's record at the trial point from the group's
+                // registers (bnd_record_thread's values): lane 3 the base
+                // position, lane a the variant and step of parameter a
+                const double ea[3] = {__shfl(e, 0, 4), __shfl(e, 1, 4), __shfl(e, 2, 4)};
+                if (pw >= 0) {
+#pragma unroll
+                    for (int a = 0; a < 3; ++a)
+                        if (a < pw) {
+                            const int comp = (pcm >> (2 * a)) & 3;
+                            if (comp == 0) base[0] = ea[a];
+                            if (comp == 1) base[1] = ea[a];
+                            if (comp == 2) base[2] = ea[a];
+                        }
+                    double *br = &T.brec[(size_t)b * BREC];
+                    if (k == 3) {
+                        br[0] = base[0];
+                        br[1] = base[1];
+                        br[2] = base[2];
+                    } else if (k < pw) {
+                        const int comp = (pcm >> (2 * k)) & 3;
+                        br[3 + 3 * k] = comp == 0 ? ep : base[0];
+                        br[4 + 3 * k] = comp == 1 ? ep : base[1];
+                        br[5 + 3 * k] = comp == 2 ? ep : base[2];
+                        br[12 + k] = stp;
+                    }
+                }
+            } else {
+                // the table walk reads what the group's lanes stored
+                __syncthreads();
+                if (k == 0) bnd_record_thread(P, b, T.ext_pert, T.step, T.brec, 0);
+            }
+        }
+    } else if (T.rec) {
+        // four camera-frames per workgroup, 16 lanes each, on the first 64
+        // lanes (k_backsub_trial's branch); the others join the barriers
+        const bool wk = tid < 64;
+        const int cf = ob * 4 + (tid >> 4);
+        const int v = tid & 15;
+        int off = 0, nv = -1;
+        if (wk && cf < P.ncf) {
+            off = P.cf_var_off[cf];
+            nv = P.cf_var_off[cf + 1] - off - 1;
+        }
+        if (v < nv) {
+            const int j = P.cf_var_param[off + 1 + v];
+            trial_one(P, T, j, x[j], pn, xn);
+        }
+        __syncthreads();
+        if (v <= nv) {
+            const int p = P.cf_var_param[off + v];  // -1: the base record
+            const long long ov_idx = p >= 0 ? P.p_vidx[p] : -1;
+            const double ov_val = p >= 0 ? T.ext_pert[p] : 0.;
+            camera_record_fast(P, cf, ov_idx, ov_val, &T.recs[(size_t)(off + v) * CAMREC],
+                               p >= 0 ? P.p_attr[p] : -1);
+        }
+    } else if (tid < 64) {
+        const int kq = ob * 64 + tid;
+        if (kq < T.nother) {
+            const int j = T.other[kq];
+            trial_one(P, T, j, x[j], pn, xn);
+        }
+    }
+    // one partial per workgroup, the 64-leaf fixed tree of k_backsub_trial
+    if (leaf >= 0) {
+        red[leaf] = pn;
+        red[64 + leaf] = xn;
+    }
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if (tid < w) {
+            red[tid] += red[tid + w];
+            red[64 + tid] += red[64 + tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        T.partial[lb] = red[0];
+        T.partial[T.rstride + lb] = red[64];
+    }
+}
+
 // The trial point's parameter pass with its records, for plans without a
 // solved bundle (C5): workgroups [0, ncfb) take four camera-frames each (16
 // lanes per camera-frame: its parameters' trial values, then after the
@@ -3696,7 +3978,19 @@ void launch_backsub_trial(hipStream_t s, const DevProblem &P, const double *W, c
                           double *x, const TrialFold &T) {
     const int nbb = nblk(P.nB, 64);
     const int g = trial_fold_parts(P, T.nother, T.rec != 0);
-    if (g > 0) k_backsub_trial<<<g, 64, 0, s>>>(P, U, W, Wg, tb, Lb, xR, x, nbb, T);
+    if (g <= 0) return;
+    if (!T.group) {
+        k_backsub_trial<<<g, 64, 0, s>>>(P, U, W, Wg, tb, Lb, xR, x, nbb, T);
+        return;
+    }
+    // the other workgroups first, padded to a multiple of 8 (k_backsub_trial_g)
+    const int nob = g - nbb, gg = ((nob + 7) & ~7) + nbb;
+    if (!W)
+        k_backsub_trial_g<false, false><<<gg, 256, 0, s>>>(P, U, W, Wg, tb, Lb, xR, x, nbb, nob, T);
+    else if (P.wst == 18)
+        k_backsub_trial_g<true, true><<<gg, 256, 0, s>>>(P, U, W, Wg, tb, Lb, xR, x, nbb, nob, T);
+    else
+        k_backsub_trial_g<true, false><<<gg, 256, 0, s>>>(P, U, W, Wg, tb, Lb, xR, x, nbb, nob, T);
 }
 
 void launch_obs_wtx(hipStream_t s, const DevProblem &P, const double *W, const double *xR,

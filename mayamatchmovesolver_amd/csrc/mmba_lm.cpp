@@ -26,6 +26,11 @@
 
 namespace mmba {
 
+// Unpinned form of the trial back substitution (MMBA_PATH_BACKSUB_GROUP and,
+// with the group form, MMBA_PATH_BACKSUB_ONEPASS): DESIGN.md section 4.
+constexpr bool kBacksubGroup = true;
+constexpr bool kBacksubGroupOnepass = true;
+
 static double wall_now() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch())
         .count();
@@ -859,11 +864,20 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
         if (trial_fold_ok) {
             // the trial point's parameter pass rides in the back substitution
             // (the last damped solve before a trial is the one it keeps)
-            // one pass (MMBA_PATH_BACKSUB_ONEPASS = 1): the bundle threads form
-            // u_i = W_i^T x_cf(i) themselves (the same sums), no k_obs_wtx --
-            // measured slower on C4 (4,299 against 4,406 LM it/s, same box,
-            // profiles/r6_ab2/: the gathered 144-B W rows), so opt-in
-            const bool onepass = path_choice(MMBA_PATH_BACKSUB_ONEPASS) == 1;
+            // one pass (MMBA_PATH_BACKSUB_ONEPASS = 1): the back substitution
+            // forms u_i = W_i^T x_cf(i) itself (the same sums), no k_obs_wtx.
+            // With one thread per bundle it measured slower on C4 (4,299
+            // against 4,406 LM it/s, same box, profiles/r6_ab2/: four gathered
+            // 144-B W rows in series per thread), so there it stays opt-in.
+            // group (MMBA_PATH_BACKSUB_GROUP): four lanes per bundle, a lane per
+            // observation and per parameter (k_backsub_trial_g, the same sums);
+            // sharded plans take it too, rolling-shutter plans stay on the
+            // thread-per-bundle kernel.  Unset keys: kBacksubGroup, and with
+            // the group form kBacksubGroupOnepass
+            const int gpin = path_choice(MMBA_PATH_BACKSUB_GROUP);
+            const int opin = path_choice(MMBA_PATH_BACKSUB_ONEPASS);
+            const bool group = !P.rs && !rs_bnd && (gpin < 0 ? kBacksubGroup : gpin == 1);
+            const bool onepass = opin < 0 ? (group && kBacksubGroupOnepass) : opin == 1;
             if (!onepass) launch_obs_wtx(s, PS, d_W, d_xR, d_U);
             TrialFold T;
             T.x = d_x;
@@ -885,6 +899,9 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
             T.rec = trial_rec ? 1 : 0;
             T.recs = d_recs;
             T.brec = d_brec;
+            T.group = group ? 1 : 0;
+            T.bobs_rp = d_bobs_rp;
+            T.brec_fwd = brec_fwd ? 1 : 0;
             launch_backsub_trial(s, PS, onepass ? d_W : nullptr, d_Wg, d_tb, d_Lb, d_xR, d_U, d_xs, T);
             trial_folded = true;
             params_at = nullptr;  // the attribute block now holds the trial point

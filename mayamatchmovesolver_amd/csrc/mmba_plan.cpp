@@ -1327,6 +1327,14 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     D.brec = d_brec;
     D.bobs_off = upload(bobs_off);
     D.bobs = upload(bobs);
+    {
+        std::vector<int2> rp(M);
+        for (int q = 0; q < M; ++q) {
+            const int cf = d_cf[bobs[q]];
+            rp[q] = make_int2(cf_roff[cf], cf_pc[cf]);
+        }
+        d_bobs_rp = upload(rp);
+    }
     D.cam_lpar_off = upload(cam_lpar_off);
     {
         bool any_inst = false;
@@ -1381,6 +1389,7 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         // fast parentless bundles: value indices of the translate and the
         // component each parameter sets
         bool ok = nB > 0;
+        bool fwd = true;  // brec_fwd: each parameter sets its own, distinct component
         std::vector<int4> vx(std::max(nB, 1), make_int4(-1, -1, -1, 0));
         std::vector<int> pcomp(std::max(nB, 1), 0);
         for (int b = 0; b < nB && ok; ++b) {
@@ -1401,19 +1410,27 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
             const int4 p4 = bnd_p4[b];
             if (p4.w < 0) continue;  // generic bundle: not read through the table
             const int ps[3] = {p4.x, p4.y, p4.z};
+            int seen = 0;
             for (int a = 0; a < p4.w && ok; ++a) {
                 const int pa = pr->param_attr[ps[a]];
                 int comp = -1;
                 for (int k = 0; k < 3; ++k)
                     if (pr->tfm_attrs[9 * t + k] == pa) comp = k;
-                if (comp < 0) ok = false;
-                else pcomp[b] |= comp << (2 * a);
+                if (comp < 0) {
+                    ok = false;
+                } else {
+                    pcomp[b] |= comp << (2 * a);
+                    if ((seen >> comp) & 1 || param_vidx[ps[a]] != (long long)ix[comp])
+                        fwd = false;
+                    seen |= 1 << comp;
+                }
             }
         }
         if (ok) {
             D.bnd_vx = upload(vx);
             D.bnd_pcomp = upload(pcomp);
         }
+        brec_fwd = ok && fwd;
     }
     D.rs = rs_on ? 1 : 0;
     D.obs_tau = nullptr;

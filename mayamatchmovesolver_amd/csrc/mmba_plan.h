@@ -466,6 +466,15 @@ struct Plan {
     // the folded trial pass also builds the trial point's records (no
     // k_records launch; TrialFold::rec)
     bool trial_rec = false;
+    // the folded trial pass with a group of four lanes per bundle
+    // (MMBA_PATH_BACKSUB_GROUP; not on rolling-shutter plans):
+    // d_bobs_rp[q] = {cf_roff, cf_pc} of the camera-frame of observation
+    // bobs[q]; brec_fwd: on every fast bundle each parameter sets its own,
+    // distinct translate component of the parentless bundle (p_vidx equals
+    // that component's bnd_vx entry), so the group builds the bundle record
+    // from the values its lanes hold
+    int2 *d_bobs_rp = nullptr;
+    bool brec_fwd = false;
     // plans without a solved bundle: k_trial_prep_rec sets the trial point
     // and builds its records (no k_records launch); the parameters outside
     // every camera-frame block (globals no record reads)
