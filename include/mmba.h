@@ -641,6 +641,11 @@ typedef struct mmba_kernel_stats {
                                where the route is not taken or pinned off
                                (MMBA_PATH_NE_CF_SPLIT = 0); a group plan
                                reports its first shard's                   */
+    int32_t trial_red_folds; /* trials of this plan since it was created whose
+                               scalar reduction and LM decision rode in the
+                               gated Jacobian pass instead of their own launch
+                               (MMBA_PATH_TRIAL_RED_FOLD); a group plan
+                               reports its first shard's                   */
 } mmba_kernel_stats;
 int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                            mmba_kernel_stats *out);
@@ -715,7 +720,17 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                                       (a lane per observation of each chunk of four, a lane per
                                       parameter; same sums), 0 one thread per bundle; default:
                                       the group form, except on rolling-shutter plans */
-#define MMBA_PATH_NUM 25
+#define MMBA_PATH_TRIAL_RED_FOLD 25 /* 0: the trial's scalar reduction, LM decision and host
+                                       mirror always run as their own launch (k_reduce_multi);
+                                       1: where the next Jacobian is enqueued behind the trial
+                                       (unsharded mirrored plans on the fused Jacobian pass),
+                                       every workgroup of that pass reduces the trial's rows
+                                       and takes the decision itself, one extra workgroup
+                                       publishes slots, gate and mirror, and the launch between
+                                       the two is skipped (same bits); the factorisation flag
+                                       is then converted by the trial's back substitution.
+                                       Default: 1 */
+#define MMBA_PATH_NUM 26
 int mmba_debug_set_path(int key, int value);
 
 /* Test hook (not part of the solver seam): solve S x = r with the device

@@ -49,7 +49,8 @@ PATH_HANDBACK_DMA = 21
 PATH_PRE_HANDBACK = 22
 PATH_PRE_SCHUR = 23
 PATH_BACKSUB_GROUP = 24
-PATH_NUM = 25
+PATH_TRIAL_RED_FOLD = 25
+PATH_NUM = 26
 
 FILM_FIT_FILL = 0
 FILM_FIT_HORIZONTAL = 1
@@ -240,6 +241,7 @@ class MmbaKernelStats(C.Structure):
         ("chol_flops_alg", C.c_double),
         ("pre_handbacks", C.c_int32),
         ("ne_split_launches", C.c_int32),
+        ("trial_red_folds", C.c_int32),
     ]
 
     def as_dict(self):

@@ -206,12 +206,37 @@ struct NeEpi {
     // observations and at exit, and its XCC id
     long long *probe = nullptr;
 };
+// The trial's reduction and LM decision carried by the gated Jacobian launch
+// behind it (MMBA_PATH_TRIAL_RED_FOLD) instead of a k_reduce_multi launch
+// between the two.  Every camera-frame workgroup of k_jac_ne_u reduces the
+// trial's rows itself (reduce_row_w64: k_reduce_multi's bits), evaluates
+// lm_decide's arithmetic on its own values and returns where a closed gate
+// returns; one extra workgroup (the grid's first) does the same and publishes
+// what k_reduce_multi's last block writes: the slots, dec's five outputs, the
+// gate, the host mirror and the sequence word.  No workgroup waits for
+// another: a decision reads only the workgroup's own row values and slots
+// this launch does not write.
+// spec: rows 0..3 -> SL_PNORM, SL_XN2T, SL_FNORM, SL_JP; row 4 (nrows == 5)
+// -> SL_DNORM (the undamped solve's ||D xs||^2 by the trial).  The
+// factorisation flag is in its slot already (TrialFold::flag).
+struct TrialRed {
+    int on = 0;
+    RedSpec spec{};
+    LmDec dec{};
+    const double *partial = nullptr;
+    double *scalar = nullptr;
+    double *host = nullptr;
+    int host_n = 0;
+    unsigned *host_seq = nullptr;
+    unsigned seq = 0;
+};
 // Fused K2 (k_jac_ne_u): FD Jacobian + camera-frame normal equations in one
 // pass for uniform fast plans without global parameters (ncv = jac_ncv).
 bool jac_ne_fusable(const DevProblem &P, int ncv);
 void launch_jac_ne(hipStream_t s, const DevProblem &P, const double *recs, const double *step,
                    int solver_type, double *J, int *jcol, int *nloc, const int *stale_param,
-                   double *eu, double *ed, double *Acc, double *g, const NeEpi &E);
+                   double *eu, double *ed, double *Acc, double *g, const NeEpi &E,
+                   const TrialRed &R = TrialRed());
 // Whether launch_ne can fuse the bookkeeping (uniform camera blocks, fast
 // bundles, no global parameters).
 bool ne_epilogue_fusable(const DevProblem &P);
@@ -311,6 +336,12 @@ struct TrialFold {
     int group = 0;
     const int2 *bobs_rp = nullptr;
     int brec_fwd = 0;
+    // flag != nullptr (MMBA_PATH_TRIAL_RED_FOLD, the undamped solve whose
+    // ||D xs||^2 the trial reduces): thread 0 of workgroup 0 converts the
+    // factorisation flag to *flag_out (SL_FAIL) and clears it -- what block 0
+    // of the trial's k_reduce_multi does otherwise, one launch earlier
+    int *flag = nullptr;
+    double *flag_out = nullptr;
 };
 // Whether the trial's records can be built inside the back substitution: no
 // global parameter (every non-bundle parameter belongs to one camera-frame),

@@ -139,26 +139,37 @@ __device__ __forceinline__ void bundle_chol3(double (&A)[3][3], double (&rhs)[3]
 // reduce_row_block by one wave (a 64-thread workgroup of another launch):
 // lane t holds the block's threads t, t + 64, t + 128 and t + 192 and combines
 // them, then the lanes, in that block's tree order -- the same value.
-__device__ __forceinline__ double reduce_row_w64(const double *partial, const RedRow &rw) {
-    const bool mx = rw.is_max != 0;
+// In two steps, so that a caller can put other loads between them: row_issue
+// issues every load of a row of up to 1,536 entries (C4: 1,282) into q,
+// row_finish combines them (a longer row is loaded there, in turn).
+constexpr int RED_JB = 6;
+struct RowQ {
+    double q[4][RED_JB];
+};
+__device__ __forceinline__ void row_issue(const double *partial, const RedRow &rw, RowQ &Q) {
     const int t = threadIdx.x & 63;
-    double s[4];
-    constexpr int JB = 6;  // rows of up to 1,536 entries (C4: 1,282): every load issued first
-    if (rw.n <= 256 * JB) {
-        double q[4][JB];
+    if (rw.n <= 256 * RED_JB) {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int j = 0; j < JB; ++j) {
+            for (int j = 0; j < RED_JB; ++j) {
                 const int i = t + 64 * k + 256 * j;
-                q[k][j] = i < rw.n ? partial[rw.off + i] : 0.;
+                Q.q[k][j] = i < rw.n ? partial[rw.off + i] : 0.;
             }
+    }
+}
+__device__ __forceinline__ double row_finish(const double *partial, const RedRow &rw,
+                                             const RowQ &Q) {
+    const bool mx = rw.is_max != 0;
+    const int t = threadIdx.x & 63;
+    double s[4];
+    if (rw.n <= 256 * RED_JB) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             double v = 0.;
 #pragma unroll
-            for (int j = 0; j < JB; ++j)
-                if (t + 64 * k + 256 * j < rw.n) v = mx ? fmax(v, q[k][j]) : v + q[k][j];
+            for (int j = 0; j < RED_JB; ++j)
+                if (t + 64 * k + 256 * j < rw.n) v = mx ? fmax(v, Q.q[k][j]) : v + Q.q[k][j];
             s[k] = v;
         }
     } else {
@@ -181,6 +192,105 @@ __device__ __forceinline__ double reduce_row_w64(const double *partial, const Re
         if (t < w) r = mx ? fmax(r, o) : r + o;
     }
     return r;  // lane 0
+}
+__device__ __forceinline__ double reduce_row_w64(const double *partial, const RedRow &rw) {
+    RowQ Q;
+    row_issue(partial, rw, Q);
+    return row_finish(partial, rw, Q);
+}
+
+// lmder after a trial point (oracle/refcpu.c lm_core; mmba_lm.cpp
+// Plan::solve and lmpar_ne's undamped test), the same operations in the same
+// order as the host's, on the values of the slots the trial's reduction
+// writes (pnorm .. dnorm: squared norms) and of those earlier launches wrote
+// (f0, xn2, gnorm, fail).  Taken by values so that a workgroup which reduced
+// the rows itself (k_jac_ne_u, TrialRed) decides without reading a slot
+// another workgroup of its launch is writing.
+struct LmIn {
+    double f0, xn2, gnorm, fail, dnorm, pnorm, fnorm, jp, xn2t;
+};
+struct LmOut {
+    int go, info;
+    double ratio, delta, par;
+};
+__device__ __forceinline__ LmOut lm_decide_vals(const LmDec &d, const LmIn &v) {
+    const double p1 = .1, p5 = .5, p25 = .25, p75 = .75, p0001 = 1e-4;
+    const double epsmch = DBL_EPSILON;
+    double fnorm = d.f0 ? sqrt(v.f0) : d.fnorm;
+    double delta = d.delta, xnorm = d.xnorm, par = d.par, gnorm = d.gnorm;
+    int info = 0, go = 0;
+    double ratio = 0.;
+    bool taken = true;
+    if (d.spec) {
+        if (d.first) {
+            xnorm = sqrt(v.xn2);
+            delta = d.factor * xnorm;
+            if (delta == 0.) delta = d.factor;
+        }
+        gnorm = fnorm != 0. ? v.gnorm : 0.;
+        if (gnorm <= d.gtol) {
+            info = 4;
+            taken = false;
+        } else {
+            const double fl = v.fail;
+            const bool ok0 = fl == 0.;
+            const double dxnorm = ok0 ? sqrt(v.dnorm) : HUGE_VAL;
+            const double fp = dxnorm - delta;
+            // a dataflow timeout (flag >= 2) makes the host solve again
+            taken = fl < 2. && fp <= p1 * delta;
+            par = 0.;
+        }
+    }
+    if (taken) {
+        const double pnorm = sqrt(v.pnorm);
+        if (d.first) delta = fmin(delta, pnorm);
+        const double fnorm1 = sqrt(v.fnorm);
+        double actred = -1.;
+        if (p1 * fnorm1 < fnorm) {
+            const double d1 = fnorm1 / fnorm;
+            actred = 1. - d1 * d1;
+        }
+        const double temp1 = sqrt(v.jp) / fnorm;
+        const double temp2 = (sqrt(par) * pnorm) / fnorm;
+        const double prered = temp1 * temp1 + temp2 * temp2 / p5;
+        const double dirder = -(temp1 * temp1 + temp2 * temp2);
+        if (prered != 0.) ratio = actred / prered;
+        if (ratio <= p25) {
+            double temp;
+            if (actred >= 0.)
+                temp = p5;
+            else
+                temp = p5 * dirder / (dirder + p5 * actred);
+            if (p1 * fnorm1 >= fnorm || temp < p1) temp = p1;
+            delta = temp * fmin(delta, pnorm / p1);
+            par /= temp;
+        } else if (par == 0. || ratio >= p75) {
+            delta = pnorm / p5;
+            par = p5 * par;
+        }
+        const bool accept = ratio >= p0001;
+        if (accept) xnorm = sqrt(v.xn2t);
+        if (fabs(actred) <= d.ftol && prered <= d.ftol && p5 * ratio <= 1.) info = 1;
+        if (delta <= d.xtol * xnorm) info = 2;
+        if (fabs(actred) <= d.ftol && prered <= d.ftol && p5 * ratio <= 1. && info == 2) info = 3;
+        if (info == 0) {
+            if (d.nfev >= d.maxfev) info = 5;
+            if (fabs(actred) <= epsmch && prered <= epsmch && p5 * ratio <= 1.) info = 6;
+            if (delta <= epsmch * xnorm) info = 7;
+            if (gnorm <= epsmch) info = 8;
+        }
+        go = (accept && info == 0) ? 1 : 0;
+    }
+    return LmOut{go, taken ? info : -100 - info, ratio, delta, par};
+}
+// the decision's record: slots out[0..4] and the gate of the launches behind it
+__device__ __forceinline__ void lm_publish(const LmDec &d, const LmOut &o, double *scalar) {
+    scalar[d.s_out] = o.go;
+    scalar[d.s_out + 1] = o.ratio;
+    scalar[d.s_out + 2] = o.delta;
+    scalar[d.s_out + 3] = o.par;
+    scalar[d.s_out + 4] = o.info;
+    __hip_atomic_store(d.gate, o.go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Every row of spec at once (the last workgroup of a folded launch): each
@@ -1199,15 +1309,17 @@ struct EpiPre {
     double xv;  // x[p] (do_xn)
     double fn;  // ||f|| (do_gn)
 };
+// own (k_jac_ne_u with a TrialRed): ||f||^2 is fsq_own, as the workgroup reduced
+// it itself, instead of the slot E.fnorm_sq its launch's extra workgroup writes
 template <int PC>
 __device__ __forceinline__ EpiPre epi_preload(const DevProblem &P, const NeEpi &E, int cf,
-                                              int lane) {
+                                              int lane, bool own = false, double fsq_own = 0.) {
     EpiPre q{-1, 0., 0., 0.};
     if (!E.on || lane >= PC) return q;
     q.p = P.cf_var_param[P.cf_var_off[cf] + 1 + lane];
     q.dg = E.diag[q.p];
     if (E.do_xn) q.xv = E.x[q.p];
-    if (E.do_gn) q.fn = E.fnorm_sq ? sqrt(*E.fnorm_sq) : E.fnorm;
+    if (E.do_gn) q.fn = own ? sqrt(fsq_own) : E.fnorm_sq ? sqrt(*E.fnorm_sq) : E.fnorm;
     return q;
 }
 // epi_param with its loads done (same operations, same bits)
@@ -1490,12 +1602,102 @@ __global__ void __launch_bounds__(64 * NW) k_ne_cf_u(DevProblem P, const double 
 // parameters) in the same pass -- the J blocks are written once for the
 // Schur / ||J p|| passes and never re-read here (k_ne_cf_u's 19 MB on C4).
 // Same per-lane summation order as k_ne_cf_u with its NW.
+//
+// R.on (MMBA_PATH_TRIAL_RED_FOLD): the launch also carries the reduction and
+// the LM decision of the trial ahead of it (TrialRed, mmba_kernels.h).
+
+// The extra workgroup of a k_jac_ne_u launch with a TrialRed: what the last
+// block of the trial's k_reduce_multi writes -- the rows' slots, the
+// decision's record and gate, then the host mirror by wave 0 behind its own
+// system fence and the sequence word the host polls.
+__device__ __forceinline__ void jac_ne_publish(const TrialRed &R, const LmIn &v, const LmOut &o) {
+    if (threadIdx.x == 0) {
+        const double val[5] = {v.pnorm, v.xn2t, v.fnorm, v.jp, v.dnorm};
+#pragma unroll
+        for (int r = 0; r < 5; ++r)
+            if (r < R.spec.nrows) R.scalar[R.spec.row[r].slot] = val[r];
+        lm_publish(R.dec, o, R.scalar);
+    }
+    if (!R.host) return;
+    if (threadIdx.x < 64) {
+        // (lane 0's stores above precede its wave's loads of the same slots)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        for (int i = threadIdx.x; i < R.host_n; i += 64)
+            R.host[i] = __hip_atomic_load(&R.scalar[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (R.host_seq) {
+            __threadfence_system();  // the wave's mirror stores visible to the host
+            if (threadIdx.x == 0)
+                __hip_atomic_store(R.host_seq, R.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// The trial's rows reduced by the workgroup's NW waves, wave w row w and, in
+// two-wave workgroups, w + 2 (any further row in turn), into sTr (valid
+// after the caller's next barrier), and the decision's slots that no
+// workgroup of the launch writes -- SL_DNORM among them only when no row
+// carries it.  trial_rows_issue issues the loads, trial_rows_finish combines
+// them: the caller's own loads go between the two.
+struct TrialRows {
+    RowQ Q0, Q1;
+    int r0, nred;
+    bool dn_dup;
+};
+template <int NW>
+__device__ __forceinline__ void trial_rows_issue(const TrialRed &R, LmIn &tin, TrialRows &T) {
+    const LmDec &d = R.dec;
+    const int nr = R.spec.nrows;
+    // the ||D xs||^2 row is the ||D p||^2 row again (p = -xs): the same
+    // entries through the same tree, the same value
+    T.dn_dup = nr == 5 && R.spec.row[4].off == R.spec.row[0].off &&
+               R.spec.row[4].n == R.spec.row[0].n &&
+               R.spec.row[4].is_max == R.spec.row[0].is_max;
+    T.nred = T.dn_dup ? 4 : nr;
+    T.r0 = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    if (T.r0 < T.nred) row_issue(R.partial, R.spec.row[T.r0], T.Q0);
+    if constexpr (NW == 2)
+        if (T.r0 + NW < T.nred) row_issue(R.partial, R.spec.row[T.r0 + NW], T.Q1);
+    tin.f0 = R.scalar[d.s_f0];
+    tin.xn2 = R.scalar[d.s_xn2];
+    tin.gnorm = R.scalar[d.s_gnorm];
+    tin.fail = R.scalar[d.s_fail];
+    if (nr < 5) tin.dnorm = R.scalar[d.s_dnorm];
+}
+template <int NW>
+__device__ __forceinline__ void trial_rows_finish(const TrialRed &R, double *sTr,
+                                                  const TrialRows &T) {
+    const bool l0 = (threadIdx.x & 63) == 0;
+    if (T.r0 < T.nred) {
+        const double v = row_finish(R.partial, R.spec.row[T.r0], T.Q0);
+        if (l0) sTr[T.r0] = v;
+    }
+    if constexpr (NW == 2)
+        if (T.r0 + NW < T.nred) {
+            const double v = row_finish(R.partial, R.spec.row[T.r0 + NW], T.Q1);
+            if (l0) sTr[T.r0 + NW] = v;
+        }
+    for (int r = T.r0 + (NW == 2 ? 2 : 1) * NW; r < T.nred; r += NW) {
+        const double v = reduce_row_w64(R.partial, R.spec.row[r]);
+        if (l0) sTr[r] = v;
+    }
+}
+// lm_decide's arithmetic on the workgroup's own row values
+__device__ __forceinline__ LmOut trial_decide(const TrialRed &R, const double *sTr, LmIn &tin,
+                                              bool dn_dup) {
+    tin.pnorm = sTr[0];
+    tin.xn2t = sTr[1];
+    tin.fnorm = sTr[2];
+    tin.jp = sTr[3];
+    if (R.spec.nrows == 5) tin.dnorm = dn_dup ? sTr[0] : sTr[4];
+    return lm_decide_vals(R.dec, tin);
+}
+
 template <int PC, int NW, bool GEN>
 __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
     DevProblem P, const double *__restrict__ recs, const double *__restrict__ step,
     int solver_type, double *__restrict__ J, int *__restrict__ jcol, int *__restrict__ nloc,
     const int *__restrict__ stale_param, double *__restrict__ eu, double *__restrict__ ed,
-    double *Acc, double *g, NeEpi E) {
+    double *Acc, double *g, NeEpi E, TrialRed R) {
     constexpr int NCC = PC * (PC + 1) / 2, NE = NCC + PC;
     __shared__ double wsum[NW][NE];
     // the camera-frame's records, variant parameters and steps: staged once
@@ -1504,36 +1706,83 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
     __shared__ int sPv[PC];
     __shared__ double sSt[PC];
     __shared__ int sHdr[3];  // nv, frame, stale column
+    __shared__ double sTr[5];  // R.on: the trial's rows as this workgroup reduced them
     // a Jacobian enqueued ahead of the host's decision runs only when the
-    // device's restatement of that decision (lm_decide) let it
-    if (E.gate && __hip_atomic_load(E.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+    // device's restatement of that decision (lm_decide) let it: read from the
+    // gate k_reduce_multi wrote, or (R.on) taken here
+    if (!R.on && E.gate &&
+        __hip_atomic_load(E.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
         return;
-    const int cf = xcd_remap(blockIdx.x, gridDim.x);
-    long long *pr = (E.probe && threadIdx.x == 0) ? E.probe + 5 * (size_t)cf : nullptr;
-    if (pr) pr[0] = (long long)wall_clock64();
-    const int o0 = P.cf_obs_off[cf], o1 = P.cf_obs_off[cf + 1];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    LmIn tin{};
+    TrialRows TR;
+    TR.dn_dup = false;
+    // R.on: workgroup 0 publishes the decision and computes no Jacobian --
+    // dispatched first, so the host's mirror does not wait for a round of
+    // Jacobian work where the grid exceeds one residency; workgroups 1..7 idle,
+    // so camera-frame block b - 8 still runs on XCD b mod 8 and the
+    // camera-frame -> XCD map is that of ncf workgroups
+    const int pad = R.on ? 8 : 0;
+    const int ncf = (int)gridDim.x - pad;
+    if ((int)blockIdx.x < pad) {
+        if (blockIdx.x != 0) return;
+        trial_rows_issue<NW>(R, tin, TR);
+        trial_rows_finish<NW>(R, sTr, TR);
+        __syncthreads();
+        const LmOut out = trial_decide(R, sTr, tin, TR.dn_dup);
+        jac_ne_publish(R, tin, out);
+        return;
+    }
+    const int cf = xcd_remap((int)blockIdx.x - pad, ncf);
+    long long *pr = (E.probe && threadIdx.x == 0) ? E.probe + 5 * (size_t)cf : nullptr;
+    const long long t_in = pr ? (long long)wall_clock64() : 0;  // stored once the gate is known open
+    const int o0 = P.cf_obs_off[cf], o1 = P.cf_obs_off[cf + 1];
     const bool lmder = solver_type == MMBA_SOLVER_CMINPACK_LMDER;
     const bool solved = P.cf_pc[cf] == PC && own_cf(P, cf);  // sharded: owner's blocks only
     {
+        // the staging's first loads, then (R.on) the loads of the trial's rows
+        // and of the decision's slots, then the staging's dependent loads:
+        // the rows come from other XCDs' workgroups (no L2 hit), and loads
+        // return in order, so the records' lines, which the back substitution
+        // left in this XCD's L2, are asked for first and the rows are in
+        // flight while the dependent loads go round
+        constexpr int KT = ((PC + 1) * CAMREC + 64 * NW - 1) / (64 * NW);
         const int voff = P.cf_var_off[cf];
         const int nv = min(P.cf_var_off[cf + 1] - voff - 1, PC);
-        for (int t = tid; t < (nv + 1) * CAMREC; t += 64 * NW)
-            sRec[t] = recs[(size_t)voff * CAMREC + t];
+        double rv[KT];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const int t = tid + 64 * NW * k;
+            rv[k] = t < (nv + 1) * CAMREC ? recs[(size_t)voff * CAMREC + t] : 0.;
+        }
+        const int p = (tid < PC && tid < nv) ? P.cf_var_param[voff + 1 + tid] : -1;
+        const int fr = P.cf_frame[cf];
+        if (R.on) trial_rows_issue<NW>(R, tin, TR);
+        const double stv = p >= 0 ? step[p] : 1.;
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const int t = tid + 64 * NW * k;
+            if (t < (nv + 1) * CAMREC) sRec[t] = rv[k];
+        }
         if (tid < PC) {
-            const int p = tid < nv ? P.cf_var_param[voff + 1 + tid] : -1;
             sPv[tid] = p;
-            sSt[tid] = tid < nv ? step[p] : 1.;
+            sSt[tid] = stv;
         }
         if (tid == 0) {
-            const int fr = P.cf_frame[cf];
             sHdr[0] = nv;
             sHdr[1] = fr;
             sHdr[2] = stale_param[fr];
         }
     }
+    if (R.on) trial_rows_finish<NW>(R, sTr, TR);
     __syncthreads();
-    if (pr) pr[1] = (long long)wall_clock64();
+    // every workgroup takes the decision on its own values: no ticket, no
+    // wait; a closed gate returns here, nothing written before it
+    if (R.on && trial_decide(R, sTr, tin, TR.dn_dup).go == 0) return;
+    if (pr) {
+        pr[0] = t_in;
+        pr[1] = (long long)wall_clock64();
+    }
     JacCf<PC> C;
     C.rcf = sRec;
 #pragma unroll
@@ -1611,7 +1860,9 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
         }
         // (loaded here: preloaded before the loop they cost this 232-VGPR
         // kernel its second wave per SIMD)
-        epi_params_wave<PC>(P, E, cf, ln, d, gp, epi_preload<PC>(P, E, cf, ln));
+        // (R.on: ||f||^2 is the workgroup's own row value, not the slot the
+        // extra workgroup is writing)
+        epi_params_wave<PC>(P, E, cf, ln, d, gp, epi_preload<PC>(P, E, cf, ln, R.on != 0, sTr[2]));
     }
     if (pr) {
         pr[3] = (long long)wall_clock64();
@@ -2163,83 +2414,12 @@ __global__ void __launch_bounds__(256) k_trial_prep(
     block_partial<false>(xn, red, partial + rstride);
 }
 
-// lmder after a trial point (oracle/refcpu.c lm_core; mmba_lm.cpp
-// Plan::solve and lmpar_ne's undamped test), the same operations in the same
-// order as the host's, from the slots this reduction just wrote.
+// lm_decide_vals from the slots this reduction just wrote.
 __device__ void lm_decide(const LmDec &d, double *scalar) {
-    const double p1 = .1, p5 = .5, p25 = .25, p75 = .75, p0001 = 1e-4;
-    const double epsmch = DBL_EPSILON;
-    double fnorm = d.f0 ? sqrt(scalar[d.s_f0]) : d.fnorm;
-    double delta = d.delta, xnorm = d.xnorm, par = d.par, gnorm = d.gnorm;
-    int info = 0, go = 0;
-    double ratio = 0.;
-    bool taken = true;
-    if (d.spec) {
-        if (d.first) {
-            xnorm = sqrt(scalar[d.s_xn2]);
-            delta = d.factor * xnorm;
-            if (delta == 0.) delta = d.factor;
-        }
-        gnorm = fnorm != 0. ? scalar[d.s_gnorm] : 0.;
-        if (gnorm <= d.gtol) {
-            info = 4;
-            taken = false;
-        } else {
-            const double fl = scalar[d.s_fail];
-            const bool ok0 = fl == 0.;
-            const double dxnorm = ok0 ? sqrt(scalar[d.s_dnorm]) : HUGE_VAL;
-            const double fp = dxnorm - delta;
-            // a dataflow timeout (flag >= 2) makes the host solve again
-            taken = fl < 2. && fp <= p1 * delta;
-            par = 0.;
-        }
-    }
-    if (taken) {
-        const double pnorm = sqrt(scalar[d.s_pnorm]);
-        if (d.first) delta = fmin(delta, pnorm);
-        const double fnorm1 = sqrt(scalar[d.s_fnorm]);
-        double actred = -1.;
-        if (p1 * fnorm1 < fnorm) {
-            const double d1 = fnorm1 / fnorm;
-            actred = 1. - d1 * d1;
-        }
-        const double temp1 = sqrt(scalar[d.s_jp]) / fnorm;
-        const double temp2 = (sqrt(par) * pnorm) / fnorm;
-        const double prered = temp1 * temp1 + temp2 * temp2 / p5;
-        const double dirder = -(temp1 * temp1 + temp2 * temp2);
-        if (prered != 0.) ratio = actred / prered;
-        if (ratio <= p25) {
-            double temp;
-            if (actred >= 0.)
-                temp = p5;
-            else
-                temp = p5 * dirder / (dirder + p5 * actred);
-            if (p1 * fnorm1 >= fnorm || temp < p1) temp = p1;
-            delta = temp * fmin(delta, pnorm / p1);
-            par /= temp;
-        } else if (par == 0. || ratio >= p75) {
-            delta = pnorm / p5;
-            par = p5 * par;
-        }
-        const bool accept = ratio >= p0001;
-        if (accept) xnorm = sqrt(scalar[d.s_xn2t]);
-        if (fabs(actred) <= d.ftol && prered <= d.ftol && p5 * ratio <= 1.) info = 1;
-        if (delta <= d.xtol * xnorm) info = 2;
-        if (fabs(actred) <= d.ftol && prered <= d.ftol && p5 * ratio <= 1. && info == 2) info = 3;
-        if (info == 0) {
-            if (d.nfev >= d.maxfev) info = 5;
-            if (fabs(actred) <= epsmch && prered <= epsmch && p5 * ratio <= 1.) info = 6;
-            if (delta <= epsmch * xnorm) info = 7;
-            if (gnorm <= epsmch) info = 8;
-        }
-        go = (accept && info == 0) ? 1 : 0;
-    }
-    scalar[d.s_out] = go;
-    scalar[d.s_out + 1] = ratio;
-    scalar[d.s_out + 2] = delta;
-    scalar[d.s_out + 3] = par;
-    scalar[d.s_out + 4] = taken ? info : -100 - info;
-    __hip_atomic_store(d.gate, go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const LmIn v{scalar[d.s_f0],    scalar[d.s_xn2],   scalar[d.s_gnorm],
+                 scalar[d.s_fail],  scalar[d.s_dnorm], scalar[d.s_pnorm],
+                 scalar[d.s_fnorm], scalar[d.s_jp],    scalar[d.s_xn2t]};
+    lm_publish(d, lm_decide_vals(d, v), scalar);
 }
 
 // Several partial rows reduced in one launch, block r for row r, in the
@@ -3127,6 +3307,21 @@ __device__ __forceinline__ void trial_one(const DevProblem &P, const TrialFold &
     }
 }
 
+// The factorisation flag to its slot, then cleared (TrialFold::flag; bit 1
+// pivot, bit 2 dataflow timeout), by one thread of the trial back
+// substitution.  Every writer of the flag in the damped solve -- the bundle
+// factor (k_ne_bnd_jb / k_bundle_factor) and the reduced solve -- is an
+// earlier launch on the plan's stream, and no workgroup of the back
+// substitution writes it.  The launches between this one and the next damped
+// solve's first writer (the gated k_ne_bnd_jb's bundle factor) are the
+// trial's residual pass and k_jac_ne_u, which only read the slot: no writer
+// of the flag can run between the clear and the next solve's writers, and
+// the redundant deciders of k_jac_ne_u all read one settled value.
+__device__ __forceinline__ void backsub_flag(const TrialFold &T) {
+    *T.flag_out = (double)*T.flag;
+    *T.flag = 0;
+}
+
 // k_backsub_bundle (two-pass form: u_i from k_obs_wtx) + the trial point's
 // parameter pass: workgroups [0, nbb) back-substitute their bundles and
 // prepare those parameters from the step just formed; workgroups [nbb, ..)
@@ -3141,6 +3336,7 @@ __global__ void __launch_bounds__(64) k_backsub_trial(DevProblem P, const double
                                                       int nbb, TrialFold T) {
     __shared__ double red[256];
     double pn = 0., xn = 0.;
+    if (T.flag && blockIdx.x == 0 && threadIdx.x == 0) backsub_flag(T);
     if ((int)blockIdx.x < nbb) {
         const int b = xcd_remap(blockIdx.x, nbb) * blockDim.x + threadIdx.x;
         const int pb = b < P.nB ? P.bnd_pb[b] : 0;
@@ -3299,6 +3495,7 @@ __global__ void __launch_bounds__(256) k_backsub_trial_g(DevProblem P, const dou
                                                          int nbb, int nob, TrialFold T) {
     __shared__ double red[128];
     const int tid = threadIdx.x;
+    if (T.flag && blockIdx.x == 0 && tid == 0) backsub_flag(T);
     // physical blocks [0, nob): the camera-frame-record / T.other workgroups
     // (the longer chain: dispatched first), [nob, pad) idle, [pad, pad + nbb) the
     // bundle workgroups -- pad a multiple of 8, so bundle block bb still runs on
@@ -4262,16 +4459,21 @@ bool jac_ne_fusable(const DevProblem &P, int ncv) {
 }
 void launch_jac_ne(hipStream_t s, const DevProblem &P, const double *recs, const double *step,
                    int solver_type, double *J, int *jcol, int *nloc, const int *stale_param,
-                   double *eu, double *ed, double *Acc, double *g, const NeEpi &E) {
+                   double *eu, double *ed, double *Acc, double *g, const NeEpi &E,
+                   const TrialRed &R) {
     if (P.ncf == 0) return;
+    // R.on: eight more workgroups ahead of the camera-frames' -- the first
+    // publishes the trial's decision, seven idle keep the camera-frame -> XCD
+    // map that of P.ncf workgroups
+    const int grid = P.ncf + (R.on ? 8 : 0);
     // the 232-VGPR kernel runs 2 waves per SIMD, so 4-wave workgroups fill
     // the chip with C4's 500 segments in one round (400 observations per
     // segment: 2 waves 41.7 us, 4 waves 34.6 us, 8 waves 45.7 us)
     const long long per = (P.M + P.ncf - 1) / P.ncf;
     int nw = per > 1024 ? 8 : (per > 256 ? 4 : 2);
 #define MMBA_JN(PC, NW, GEN)                                                                  \
-    k_jac_ne_u<PC, NW, GEN><<<P.ncf, 64 * NW, 0, s>>>(P, recs, step, solver_type, J, jcol, nloc, \
-                                                        stale_param, eu, ed, Acc, g, E)
+    k_jac_ne_u<PC, NW, GEN><<<grid, 64 * NW, 0, s>>>(P, recs, step, solver_type, J, jcol, nloc, \
+                                                       stale_param, eu, ed, Acc, g, E, R)
 #define MMBA_JN_NW(PC, GEN)                                         \
     do {                                                            \
         if (nw == 8) MMBA_JN(PC, 8, GEN);                           \

@@ -283,7 +283,12 @@ bool Plan::pre_jac_ok() const {
            !(cbk && cbk->progress);
 }
 
-void Plan::pre_jac_enqueue(const double *dx, double *eu, double *ed) {
+bool Plan::trial_red_fold() const {
+    const int pin = path_choice(MMBA_PATH_TRIAL_RED_FOLD);
+    return pin < 0 ? kTrialRedFold : pin != 0;
+}
+
+void Plan::pre_jac_enqueue(const double *dx, double *eu, double *ed, const TrialRed &red) {
     NeEpi epi;
     epi.on = 1;
     epi.first = 0;  // a later iteration: the first Jacobian is never enqueued ahead
@@ -301,8 +306,10 @@ void Plan::pre_jac_enqueue(const double *dx, double *eu, double *ed) {
     epi.bnd_base = ncf;
     epi.gate = d_gate;
     epi.probe = d_k2probe;
+    // (red.on: k_jac_ne_u takes the decision itself and writes the gate the
+    // launches behind it read; its ||f||^2 is its own SL_FNORM row value)
     launch_jac_ne(s, jb_recompute() ? P_nojb() : P, d_recs, d_step, opt.solver_type, d_J, d_jcol,
-                  nloc_set ? nullptr : d_nloc, d_stale, eu, ed, d_Acc, d_g, epi);
+                  nloc_set ? nullptr : d_nloc, d_stale, eu, ed, d_Acc, d_g, epi, red);
     nloc_set = true;
     pre_jac_pending = true;
     // the bundle pass right behind it, under the same gate (round 6): the
@@ -611,9 +618,12 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
     rs.row[rs.nrows++] = {4 * pw, tparts, 0, SL_XN2T};
     rs.row[rs.nrows++] = {5 * pw, trial_blocks(P), 0, SL_FNORM};
     rs.row[rs.nrows++] = {6 * pw, trial_blocks(P), 0, SL_JP};
+    // the fail flag: converted here, unless the back substitution did
+    // (fail_early: SL_FAIL holds it and the flag is clear)
+    int *const flag = fill_dnorm && !fail_early ? d_fail : nullptr;
     if (fill_dnorm) {  // the undamped solve's ||D xs||^2 and fail flag (solve_damped_enqueue)
         rs.row[rs.nrows++] = {3 * pw, tparts, 0, SL_DNORM};
-        rs.flag_slot = SL_FAIL;
+        if (flag) rs.flag_slot = SL_FAIL;
     }
     // unsharded: the LM decision after this trial reads slots [0, SL_LAST],
     // which the reduction's last block mirrors to the host itself
@@ -627,7 +637,7 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
         T.spec = rs;
         T.partial = d_partial;
         T.scalar = d_scalar;
-        T.flag = fill_dnorm ? d_fail : nullptr;
+        T.flag = flag;
         T.host = mirror ? h_scalar : nullptr;
         T.host_n = SL_LAST + 1;
         T.ticket = d_mticket;
@@ -651,23 +661,44 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
         D.s_out = SL_DGO;
         D.gate = d_gate;
     }
-    if (!T.on) {
+    // MMBA_PATH_TRIAL_RED_FOLD: with a Jacobian about to be enqueued behind
+    // the gate, k_jac_ne_u carries the reduction, the decision and the mirror
+    // (TrialRed) and this launch is skipped -- unsharded mirrored plans only,
+    // with the flag already in its slot, no speculative hand-back riding on
+    // the decision's slots and no timing spans; every other trial (sharded or
+    // unmirrored plans, the last trial of a solve, no fusable Jacobian ahead)
+    // reduces in its own launch as before
+    const bool hb_enq = dec && pre_hb_on && !b15;
+    TrialRed R;
+    if (dec && jac_ahead && nranks == 1 && !b15 && mirror && seq_poll && !hb_enq && !timing &&
+        !T.on && !flag && trial_red_fold()) {
+        R.on = 1;
+        R.spec = rs;
+        R.dec = D;
+        R.partial = d_partial;
+        R.scalar = d_scalar;
+        R.host = h_scalar;
+        R.host_n = SL_LAST + 1;
+        R.host_seq = h_seq;
+        R.seq = ++seq_next;
+        seq_pending = true;  // the mirror is pending on the Jacobian launch
+        ++trial_red_folds;
+    } else if (!T.on) {
         const bool sq = mirror && seq_poll;
         if (sq) ++seq_next;
-        launch_reduce_multi(s, d_partial, rs, d_scalar, fill_dnorm ? d_fail : nullptr,
-                            mirror ? h_scalar : nullptr, SL_LAST + 1, d_mticket,
-                            sq ? h_seq : nullptr, seq_next, D);
+        launch_reduce_multi(s, d_partial, rs, d_scalar, flag, mirror ? h_scalar : nullptr,
+                            SL_LAST + 1, d_mticket, sq ? h_seq : nullptr, seq_next, D);
         seq_pending = sq;
     }
     if (b15)  // ||J p||^2 of J = J_s + f c^T (no host mirror on these plans; rotated basis)
         launch_b15_jp(s, n, d_xs15r, d_g, d_c15r, d_b15k + 4, d_scalar + SL_JP);
     mirror_pending = mirror;
-    pre_hb_enq = dec && pre_hb_on && !b15;
+    pre_hb_enq = hb_enq;
     if (pre_hb_enq)  // (the previous trial's kernel precedes it on s_hb[0]: no wait)
         MMBA_HIP(hipEventRecord(ev_hb[3], s));
     if (dec && jac_ahead) {  // the next Jacobian's first launch, gated on the device's decision
         stage_slots();
-        pre_jac_enqueue(d_wa2, eu, ed);
+        pre_jac_enqueue(d_wa2, eu, ed, R);
     }
     if (pre_hb_enq) {  // behind the decision, beside the gated Jacobian
         MMBA_HIP(hipStreamWaitEvent(s_hb[0], ev_hb[3], 0));
@@ -692,6 +723,7 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
         std::this_thread::sleep_for(std::chrono::milliseconds(2 * (long long)comm_timeout_ms()));
     }
     if (!red_defer_ok()) flush_red();
+    fail_early = false;
     if (b15 && !b15_inner) {
         // B15: (M + U B U^T) xs = u + s c from M z_u = u and M z_c = c, the
         // same damped factorisation formed twice (the right-hand side rides
@@ -902,6 +934,13 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
             T.group = group ? 1 : 0;
             T.bobs_rp = d_bobs_rp;
             T.brec_fwd = brec_fwd ? 1 : 0;
+            if (dnorm_by_trial && nranks == 1 && !b15 && trial_red_fold()) {
+                // the flag to SL_FAIL here, a launch ahead of the trial's
+                // reduction: the deciders of k_jac_ne_u read the slot
+                T.flag = d_fail;
+                T.flag_out = d_scalar + SL_FAIL;
+                fail_early = true;
+            }
             launch_backsub_trial(s, PS, onepass ? d_W : nullptr, d_Wg, d_tb, d_Lb, d_xR, d_U, d_xs, T);
             trial_folded = true;
             params_at = nullptr;  // the attribute block now holds the trial point

@@ -488,7 +488,18 @@ struct Plan {
     const double *pre_jac_x = nullptr;
     int *d_gate = nullptr;
     bool pre_jac_ok() const;
-    void pre_jac_enqueue(const double *dx, double *eu, double *ed);
+    // red (MMBA_PATH_TRIAL_RED_FOLD): the trial's reduction, decision and
+    // host mirror ride in the gated k_jac_ne_u launch (TrialRed) instead of a
+    // k_reduce_multi launch ahead of it
+    void pre_jac_enqueue(const double *dx, double *eu, double *ed,
+                         const TrialRed &red = TrialRed());
+    // Unpinned choice of MMBA_PATH_TRIAL_RED_FOLD
+    static constexpr bool kTrialRedFold = true;
+    bool trial_red_fold() const;
+    // the last damped solve's back substitution converted the factorisation
+    // flag to SL_FAIL and cleared it (TrialFold::flag): the trial's reduction
+    // leaves both alone
+    bool fail_early = false;
     // the trial's slots staged (D2H copy unless mirrored, then an event)
     // before the pre-enqueued Jacobian: read_slots(0, SL_LAST) only waits
     bool slots_staged = false;
@@ -613,6 +624,7 @@ struct Plan {
     bool pre_hb_on = false, pre_hb_enq = false;
     long long pre_handbacks = 0;  // solves whose lists the speculative hand-back stored
     long long ne_split_launches = 0;  // k_ne_cf_split launches (launch_ne took the split branch)
+    long long trial_red_folds = 0;    // trials reduced and decided inside k_jac_ne_u (TrialRed)
     double *pre_hb_map[3] = {nullptr, nullptr, nullptr};
 };
 
