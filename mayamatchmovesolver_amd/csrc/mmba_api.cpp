@@ -421,22 +421,36 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing, mmba_kernel_stats
         out->chol_launches = p.chol_n;
         out->chol_ms_avg = p.chol_n ? p.chol_ms / p.chol_n : 0.;
         out->reduced_dim = p.nR;
-        out->reduced_kind = p.band ? (p.bs.use_bd ? 3 : 0) : (p.dense ? 2 : 1);
-        out->dataflow_fallback = p.bs.df_off ? 1 : 0;
+        using Reduced = Plan::Reduced;
+        const Reduced kind = p.reduced_now();
+        const BandSolver &b = p.bs;
+        out->dataflow_fallback = b.df_off ? 1 : 0;
+        switch (kind) {  // reduced_kind, band_solver: the ABI's numbers
+        case Reduced::BlockDiag:
+            out->reduced_kind = 3;
+            out->band_solver = 5;
+            break;
+        case Reduced::Pcr:
+            out->reduced_kind = 0;
+            out->band_solver = 3;
+            break;
+        case Reduced::Band:
+            out->reduced_kind = 0;
+            out->band_solver = p.sep_pcr_now() ? 4 : b.use_bcr ? 2 : 1;
+            break;
+        case Reduced::Dense:
+            out->reduced_kind = 2;
+            break;
+        case Reduced::TiledNarrow:
+        case Reduced::Tiled:
+            out->reduced_kind = 1;
+            break;
+        }
         out->shards_replicated = p.replicated ? 1 : 0;
         out->spec_replays = p.spec_replays;
         out->pre_handbacks = (int32_t)p.pre_handbacks;
         out->ne_split_launches = (int32_t)p.ne_split_launches;
         out->trial_red_folds = (int32_t)p.trial_red_folds;
-        {
-            const BandSolver &b = p.bs;
-            out->band_solver = !p.band ? 0
-                               : b.use_bd ? 5
-                               : (b.pcr_int && !b.df_off) ? 4
-                               : (b.use_pcr && !b.df_off) ? 3
-                               : b.use_bcr ? 2
-                               : 1;
-        }
         // Algorithmic bytes: B_J = 48 + 8 p_c (p_b + p_g) per
         // observation for the Jacobian + normal-equation pass -- the Hcb block
         // against its bundle's p_b parameters and the Hcg coupling to the p_g
@@ -456,7 +470,7 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing, mmba_kernel_stats
         out->jac_bytes = bj * p.M;
         out->resid_bytes = 48.0 * p.M;
         // reduced-system flops per factorisation as each solver performs them
-        if (p.band && p.bs.use_pcr && !p.bs.df_off) {
+        if (kind == Reduced::Pcr) {
             // parallel cyclic reduction: per block and level the factor of D
             // (K^3/3), the right-hand sides of the three pivot chains (C^-1
             // with r, P, Q: K^2 (3K + 1)), the products X1, X2 (2 K^2 (K + 1)
@@ -464,7 +478,7 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing, mmba_kernel_stats
             const double K = p.bs.pcr.K;
             out->chol_flops = (double)p.bs.pcr.nblk *
                               (p.bs.pcr.nlev * (28.0 / 3.0 * K * K * K + 9.0 * K * K) + 2.0 * K * K);
-        } else if (p.band && p.bs.use_bcr) {
+        } else if (kind == Reduced::Band && b.use_bcr) {
             // block cyclic reduction: per eliminated K x K block its Cholesky
             // (K^3/3), U / V / Y / y solves (2K^3 + nG K^2 + K^2), the two
             // symmetric Schur updates (2 x K^3), the coupling (2K^3), the arrow
@@ -473,7 +487,7 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing, mmba_kernel_stats
             out->chol_flops = (p.bs.bcr.nblk - 1) * (19.0 / 3.0 * K * K * K + 5.0 * G * K * K +
                                                      G * G * K + K * K) +
                               2.0 * N * N * N / 3.0;
-        } else if (p.band && p.bs.use_bd) {
+        } else if (kind == Reduced::BlockDiag) {
             const double pc = p.ncf ? (double)p.nCF / p.ncf : 0.;  // per camera-frame block
             out->chol_flops = (double)p.nCF * pc * pc / 3.0;
         } else if (p.band) {
@@ -486,7 +500,7 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing, mmba_kernel_stats
         {
             const double G = p.nG, nb = p.nR - p.nG;
             const double arrow = nb * G * (2.0 * p.bw + G) + G * G * G / 3.0 + 4.0 * G * G;
-            if (p.band && p.bs.use_bd) {
+            if (kind == Reduced::BlockDiag) {
                 const double pc = p.ncf ? (double)p.nCF / p.ncf : 0.;
                 out->chol_flops_alg = (double)p.ncf * (pc * pc * pc / 3.0 + 4.0 * pc * pc) +
                                       nb * G * (2.0 * pc + G) + G * G * G / 3.0 + 4.0 * G * G;
@@ -496,10 +510,10 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing, mmba_kernel_stats
                 const double N = p.nR;
                 out->chol_flops_alg = N * N * N / 3.0 + 4.0 * N * N;
             }
-            if (p.band && p.bs.use_pcr && !p.bs.df_off) {
+            if (kind == Reduced::Pcr) {
                 out->band_levels = p.bs.pcr.nlev;
                 out->band_block = p.bs.pcr.K;
-            } else if (p.band && p.bs.use_bcr) {
+            } else if (kind == Reduced::Band && b.use_bcr) {
                 out->band_levels = 0;
                 for (int a = p.bs.bcr.nblk; a > 1; a = (a + 1) / 2) ++out->band_levels;
                 out->band_block = p.bs.bcr.K;

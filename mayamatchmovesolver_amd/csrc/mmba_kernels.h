@@ -78,23 +78,10 @@ void launch_dist_stats(hipStream_t s, const DevProblem &P, const double *ed, dou
                        int nparts, int rstride, double *out);
 // launch_residual (partials only) plus ||J p||^2 partials of the same blocks
 // into partial_jp (k_jp_sumsq's sum, one launch)
-// Reduction launch folded into a producer (unsharded trial point): the
-// producer's last workgroup (ticket) runs k_reduce_multi's work -- the rows
-// of spec (offsets into partial), the fail flag and the host mirror.
-struct RedTail {
-    int on = 0;
-    RedSpec spec{};
-    const double *partial = nullptr;
-    double *scalar = nullptr;
-    int *flag = nullptr;
-    double *host = nullptr;
-    int host_n = 0;
-    unsigned *ticket = nullptr;
-};
 void launch_residual_jp(hipStream_t s, const DevProblem &P, const double *recs, double *f,
                         double *eu, double *ed, double *partial, const double *J,
                         const int *jcol, const int *nloc, const double *pstep,
-                        double *partial_jp, double *dist = nullptr, const RedTail &T = RedTail());
+                        double *partial_jp, double *dist = nullptr);
 // Second evaluation of central FD columns (lmder, autoDiffType central):
 // records / bundle records / perturbed values at x + deltaB and the column
 // factor 0.5 / (|dA| + |dB|) (0: forward column).  recs == nullptr: forward.
@@ -173,13 +160,6 @@ struct NeEpi {
     const double *x = nullptr;
     double *diag = nullptr, *acnorm = nullptr, *partial = nullptr;
     int rstride = 0, cf_base = 0, bnd_base = 0;
-    // fold (unsharded k_ne_bnd_jb): the bundle pass's last workgroup (ticket)
-    // reduces the epilogue rows of spec into scalar with k_reduce_multi's
-    // arithmetic -- no separate reduction launch
-    int fold = 0;
-    RedSpec spec{};
-    double *scalar = nullptr;
-    unsigned *ticket = nullptr;
     // jb_recs != nullptr (MMBA_PATH_JB_RECOMPUTE, the fused path only): the
     // bundle pass re-evaluates each observation's three bundle columns and f
     // from the base camera record (jb_recs) and the bundle record -- the

@@ -293,93 +293,6 @@ __device__ __forceinline__ void lm_publish(const LmDec &d, const LmOut &o, doubl
     __hip_atomic_store(d.gate, o.go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Every row of spec at once (the last workgroup of a folded launch): each
-// thread issues its loads of all rows before any sum, then one fixed tree
-// per row, level by level for all rows -- per row the arithmetic of
-// reduce_row_block (and so of k_reduce_multi).
-constexpr int RED_ROWS = 8;
-__device__ __forceinline__ void reduce_rows_sc1(const RedSpec &spec, const double *partial,
-                                                double *scalar) {
-    __shared__ double red[RED_ROWS][256];
-    const int nr = spec.nrows;
-    double sv[RED_ROWS];
-#pragma unroll
-    for (int r = 0; r < RED_ROWS; ++r) {
-        sv[r] = 0.;
-        if (r < nr) {
-            const RedRow rw = spec.row[r];
-            const bool mx = rw.is_max != 0;
-            for (int i = threadIdx.x; i < rw.n; i += blockDim.x) {
-                const double q = ld_sc1(&partial[rw.off + i]);
-                sv[r] = mx ? fmax(sv[r], q) : sv[r] + q;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < RED_ROWS; ++r)
-        if (r < nr) red[r][threadIdx.x] = sv[r];
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) {
-#pragma unroll
-            for (int r = 0; r < RED_ROWS; ++r) {
-                if (r >= nr) break;
-                const bool mx = spec.row[r].is_max != 0;
-                red[r][threadIdx.x] = mx ? fmax(red[r][threadIdx.x], red[r][threadIdx.x + w])
-                                         : red[r][threadIdx.x] + red[r][threadIdx.x + w];
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < nr) scalar[spec.row[threadIdx.x].slot] = red[threadIdx.x][0];
-    __syncthreads();
-}
-
-// Last-workgroup epilogue of a launch whose workgroups stored partials with
-// st_sc1 (or an earlier launch stored them): every storing wave drains, one
-// lane adds to the ticket (agent scope), the workgroup whose add came last
-// loads every partial sc1 (MI355X guide, valid forms, first table row) and
-// reduces the rows of spec into scalar; the ticket is reset for the next
-// user.  256 threads per workgroup.
-__device__ __forceinline__ void tail_reduce(const RedSpec &spec, const double *partial,
-                                            double *scalar, unsigned *ticket) {
-    __shared__ unsigned last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0)
-        last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-               gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    reduce_rows_sc1(spec, partial, scalar);
-    if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// tail_reduce plus the rest of k_reduce_multi's work: the fail flag to its
-// slot (then cleared) and the host mirror of scalar[0, host_n).
-__device__ __forceinline__ void tail_reduce_full(const RedTail &T) {
-    __shared__ unsigned last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0)
-        last = __hip_atomic_fetch_add(T.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-               gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    reduce_rows_sc1(T.spec, T.partial, T.scalar);
-    if (threadIdx.x == 0 && T.flag && T.spec.flag_slot >= 0) {
-        T.scalar[T.spec.flag_slot] = (double)*T.flag;  // bit 1 pivot, bit 2 dataflow timeout
-        *T.flag = 0;
-    }
-    if (T.host) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        for (int i = threadIdx.x; i < T.host_n; i += blockDim.x) T.host[i] = ld_sc1(&T.scalar[i]);
-    }
-    if (threadIdx.x == 0)
-        __hip_atomic_store(T.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // -------------------------------------------------------------------------
 // Parameters: external values, FD perturbations (adjust_solveFunc.cpp:148-180,
 // cminpack fdjac2), setParameters (adjust_setParameters.cpp:174-250).
@@ -578,8 +491,7 @@ __global__ void __launch_bounds__(256) k_residual(DevProblem P, const double *__
                                                   const int *__restrict__ jcol,
                                                   const int *__restrict__ nloc,
                                                   const double *__restrict__ pstep,
-                                                  double *partial_jp, double *dist,
-                                                  const RedTail T) {
+                                                  double *partial_jp, double *dist) {
     __shared__ double red[256];
     const int lb = xcd_remap(blockIdx.x, gridDim.x);  // logical block (XCD-contiguous)
     const int i = lb * blockDim.x + threadIdx.x;
@@ -672,12 +584,7 @@ __global__ void __launch_bounds__(256) k_residual(DevProblem P, const double *__
             if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
             __syncthreads();
         }
-        if (threadIdx.x == 0) {
-            if (T.on)
-                st_sc1(&partial_jp[lb], red[0]);  // read by this launch's last workgroup
-            else
-                partial_jp[lb] = red[0];
-        }
+        if (threadIdx.x == 0) partial_jp[lb] = red[0];
         __syncthreads();
     }
     red[threadIdx.x] = s;
@@ -685,11 +592,6 @@ __global__ void __launch_bounds__(256) k_residual(DevProblem P, const double *__
     for (int w = 128; w > 0; w >>= 1) {
         if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
-    }
-    if (T.on) {
-        if (threadIdx.x == 0) st_sc1(&partial[lb], red[0]);
-        tail_reduce_full(T);
-        return;
     }
     finish_blocks<false>(red[0], partial, out, ticket, lb);
 }
@@ -1994,15 +1896,8 @@ __global__ void __launch_bounds__(NE_BND_TPB) k_ne_bnd_jb(DevProblem P, double *
     }
     if (threadIdx.x == 0) {
         const int col = E.bnd_base + xcd_remap(blockIdx.x, gridDim.x);
-        if (E.fold) {  // read by this launch's last workgroup: write-through
-            st_sc1(&E.partial[col], red[0][0]);
-            st_sc1(&E.partial[E.rstride + col], red[1][0]);
-            st_sc1(&E.partial[2 * E.rstride + col], red[2][0]);
-        } else {
-            epi_store(E, col, red[0][0], red[1][0], red[2][0]);
-        }
+        epi_store(E, col, red[0][0], red[1][0], red[2][0]);
     }
-    if (E.fold) tail_reduce(E.spec, E.partial, E.scalar, E.ticket);
 }
 
 // Per bundle: Abb (pb x pb), gB, Abg (pb x nG).  One thread per bundle.
@@ -4272,15 +4167,15 @@ void launch_residual(hipStream_t s, const DevProblem &P, const double *recs, dou
     if (P.rs)
         k_residual<false, false, true><<<nblk(P.M, 256), 256, 0, s>>>(
             P, recs, f, eu, ed, partial, out, ticket, nullptr, nullptr, nullptr, nullptr, nullptr,
-            dist, RedTail());
+            dist);
     else if (P.all_bnd_fast && P.no_lens)
         k_residual<false, true><<<nblk(P.M, 256), 256, 0, s>>>(
             P, recs, f, eu, ed, partial, out, ticket, nullptr, nullptr, nullptr, nullptr, nullptr,
-            dist, RedTail());
+            dist);
     else
         k_residual<false, false><<<nblk(P.M, 256), 256, 0, s>>>(
             P, recs, f, eu, ed, partial, out, ticket, nullptr, nullptr, nullptr, nullptr, nullptr,
-            dist, RedTail());
+            dist);
     if (!ticket && out) k_reduce_sum<<<1, 256, 0, s>>>(partial, residual_blocks(P), out);
 }
 // Per-observation reprojection (FlatScene::evaluate's out_point_list /
@@ -4319,8 +4214,8 @@ void launch_reproject(hipStream_t s, const DevProblem &P, const double *recs, do
 void launch_residual_jp(hipStream_t s, const DevProblem &P, const double *recs, double *f,
                         double *eu, double *ed, double *partial, const double *J,
                         const int *jcol, const int *nloc, const double *pstep,
-                        double *partial_jp, double *dist, const RedTail &T) {
-    if (!T.on && trial_cf_fusable(P)) {  // partials per camera-frame (trial_blocks)
+                        double *partial_jp, double *dist) {
+    if (trial_cf_fusable(P)) {  // partials per camera-frame (trial_blocks)
         if (P.pc_uniform == 6)
             k_residual_jp_cf<6><<<P.ncf, 256, 0, s>>>(P, recs, f, eu, ed, partial, J, nloc, pstep,
                                                       partial_jp, dist);
@@ -4331,13 +4226,13 @@ void launch_residual_jp(hipStream_t s, const DevProblem &P, const double *recs, 
     }
     if (P.rs)
         k_residual<true, false, true><<<nblk(P.M, 256), 256, 0, s>>>(
-            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist, T);
+            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist);
     else if (P.all_bnd_fast && P.no_lens)
         k_residual<true, true><<<nblk(P.M, 256), 256, 0, s>>>(
-            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist, T);
+            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist);
     else
         k_residual<true, false><<<nblk(P.M, 256), 256, 0, s>>>(
-            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist, T);
+            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist);
 }
 
 // compute_error_stats (adjust_base.cpp:346-372) on the device: per block the

@@ -87,6 +87,22 @@ void Plan::collect_spans() {
     ev_used = 0;
 }
 
+// ---- the reduced solver in use: the one place that reads the booleans ----
+Plan::Reduced Plan::reduced_now() const {
+    if (band)
+        return bs.use_bd ? Reduced::BlockDiag
+                         : (bs.use_pcr && !bs.df_off) ? Reduced::Pcr : Reduced::Band;
+    if (dense) return Reduced::Dense;
+    return narrow ? Reduced::TiledNarrow : Reduced::Tiled;
+}
+// such a solve fills SL_DNORM itself: no trial is asked for that norm
+bool Plan::bd_one_launch() const { return band && bs.use_bd && nG == 0 && nranks == 1; }
+bool Plan::sep_pcr_now() const { return band && bs.pcr_int && !bs.df_off; }
+bool Plan::dataflow_off() {
+    if (bs.df_off) return false;
+    return bs.df_off = true;
+}
+
 // ---- scalar slots ----
 // The trial's slots on their way to the host before anything else is
 // enqueued behind them (the pre-enqueued Jacobian): the D2H copy (unless the
@@ -102,26 +118,26 @@ bool Plan::red_defer_ok() const {
     // nG == 0: the one-launch block-diagonal solve carries them (k_bd_direct's
     // extra workgroups); a damped solve without a norm slot takes the general
     // path, whose k_schur_init does
-    return band && bs.use_bd && (nG > 0 || path_choice(MMBA_PATH_RED_BD) != 0);
+    return reduced_now() == Reduced::BlockDiag && (nG > 0 || path_choice(MMBA_PATH_RED_BD) != 0);
 }
 
 void Plan::flush_red() {
-    if (!pend_red) return;
-    pend_red = false;
+    if (!fl.pend_red) return;
+    fl.pend_red = false;
     launch_reduce_multi(s, d_partial, pend_rs, d_scalar);
 }
 
 void Plan::stage_slots() {
     flush_red();
-    const bool mirrored = mirror_pending;
+    const bool mirrored = fl.mirror_pending;
     if (!mirrored)
         MMBA_HIP(hipMemcpyAsync(h_scalar, d_scalar, sizeof(double) * (SL_LAST + 1),
                                 hipMemcpyDeviceToHost, s));
-    if (!(mirrored && seq_pending)) {
+    if (!(mirrored && fl.seq_pending)) {
         if (!ev_sync) MMBA_HIP(hipEventCreateWithFlags(&ev_sync, hipEventDisableTiming));
         MMBA_HIP(hipEventRecord(ev_sync, s));
     }
-    slots_staged = true;
+    fl.slots_staged = true;
 }
 
 // A host wait on the plan's stream: bounded through an RCCL communicator
@@ -135,10 +151,6 @@ void Plan::wait_event() {
         comm_wait(comm, s, ev_sync);
         return;
     }
-    if (!spin_wait) {
-        MMBA_HIP(hipEventSynchronize(ev_sync));
-        return;
-    }
     for (;;) {
         const hipError_t e = hipEventQuery(ev_sync);
         if (e == hipSuccess) break;
@@ -148,18 +160,18 @@ void Plan::wait_event() {
 
 void Plan::read_slots(int lo, int hi) {
     flush_red();
-    const bool mirrored = mirror_pending && lo == 0 && hi == SL_LAST;
-    mirror_pending = false;
-    const bool by_seq = mirrored && seq_pending;
-    seq_pending = false;
-    if (slots_staged && lo == 0 && hi == SL_LAST) {
-        slots_staged = false;
+    const bool mirrored = fl.mirror_pending && lo == 0 && hi == SL_LAST;
+    fl.mirror_pending = false;
+    const bool by_seq = mirrored && fl.seq_pending;
+    fl.seq_pending = false;
+    if (fl.slots_staged && lo == 0 && hi == SL_LAST) {
+        fl.slots_staged = false;
         if (!by_seq) {
             wait_event();
             return;
         }
     }
-    slots_staged = false;
+    fl.slots_staged = false;
     if (by_seq) {
         // the reduction's last block wrote the mirror, then the sequence
         // word (system-scope release): poll page-locked memory directly --
@@ -187,7 +199,7 @@ void Plan::read_slots(int lo, int hi) {
     if (!mirrored)
         MMBA_HIP(hipMemcpyAsync(h_scalar + lo, d_scalar + lo, sizeof(double) * (hi - lo + 1),
                                 hipMemcpyDeviceToHost, s));
-    if (!spin_wait || (nranks > 1 && comm && comm->bounded())) {
+    if (nranks > 1 && comm && comm->bounded()) {
         host_sync();
         return;
     }
@@ -278,9 +290,8 @@ double Plan::fun(const double *dx, double *df, double *eu, double *ed, double *d
 // unsharded plans, forward differences, no attribute rows), no callback can
 // end the solve between the trial and the Jacobian, and no timing spans run.
 bool Plan::pre_jac_ok() const {
-    return pre_jac && nranks == 1 && !central && nrows == 0 && !timing && !k2_split &&
-           ne_epilogue_fusable(P) && jac_ne_fusable(P, jac_ncv) && !(cbk && cbk->interrupt) &&
-           !(cbk && cbk->progress);
+    return pre_jac && nranks == 1 && !central && nrows == 0 && !timing && ne_epilogue_fusable(P) &&
+           jac_ne_fusable(P, jac_ncv) && !(cbk && cbk->interrupt) && !(cbk && cbk->progress);
 }
 
 bool Plan::trial_red_fold() const {
@@ -288,49 +299,118 @@ bool Plan::trial_red_fold() const {
     return pin < 0 ? kTrialRedFold : pin != 0;
 }
 
+// The fused epilogue of the Jacobian at dx: lmder's bookkeeping rides in the
+// normal-equation kernels, which leave one partial per quantity and block.
+NeEpi Plan::fused_epi(const double *dx, const JacLM &lm) const {
+    NeEpi e;
+    e.on = 1;
+    e.first = lm.first;
+    e.mode = lm.mode;
+    e.fnorm = lm.fnorm;
+    e.fnorm_sq = lm.fnorm_sq;
+    e.do_xn = lm.first;
+    e.do_gn = lm.fnorm_sq || lm.fnorm != 0.;
+    e.x = dx;
+    e.diag = d_diag;
+    e.acnorm = d_acnorm;
+    e.partial = d_partial;
+    e.rstride = pw;
+    e.cf_base = 0;
+    e.bnd_base = ncf;
+    e.probe = d_k2probe;
+    return e;
+}
+
+// Plans with fast bundles: the bundle pass forms the lam = 0 bundle factor the
+// undamped solve reads next (no k_bundle_factor launch).  Sharded too: every
+// bundle a shard touches has all its observations there; the others have
+// Abb = 0 and factor as the identity.
+static bool epi_lb0(const Plan &pl, NeEpi &e) {
+    if (!(pl.P.nbs > 0 && pl.P.JB != nullptr && pl.nB_solved > 0)) return false;
+    e.Lb = pl.d_Lb;
+    e.tb = pl.d_tb;
+    e.fail = pl.d_fail;
+    return true;
+}
+
+// the bundle pass re-evaluates the records k_jac_ne_u did not store
+static void epi_jb(const Plan &pl, NeEpi &e) {
+    if (!pl.jb_recompute()) return;
+    e.jb_recs = pl.d_recs;
+    e.jb_lmder = pl.opt.solver_type == MMBA_SOLVER_CMINPACK_LMDER ? 1 : 0;
+}
+
+// long camera-frame segments: the camera-frame normal equations over
+// NE_CF_SPLIT workgroups each (k_ne_cf_split; launch_ne decides).  Never the
+// pre-enqueued pass: k_jac_ne_u has formed those blocks.
+static void epi_cf_split(const Plan &pl, NeEpi &e) {
+    if (path_choice(MMBA_PATH_NE_CF_SPLIT) == 0) return;
+    e.cf_part = pl.d_cf_part;
+    e.cf_ticket = pl.d_cf_ticket;
+}
+
+// columns of the fused epilogue's rows: camera-frames, then bundle workgroups
+static int epi_ncol(const Plan &pl) {
+    return pl.ncf + (pl.nB_solved > 0 ? (pl.nB + NE_BND_TPB - 1) / NE_BND_TPB : 0);
+}
+
+// the epilogue's partial rows (pw apart, ncol partials each) and their slots
+static RedSpec epi_rows(int pw, int ncol, int do_xn, int do_gn, int s_zero = Plan::SL_ZERO,
+                        int s_xn2 = Plan::SL_XN2, int s_gnorm = Plan::SL_GNORM) {
+    RedSpec rs{};
+    rs.flag_slot = -1;
+    rs.row[rs.nrows++] = {0, ncol, 1, s_zero};
+    if (do_xn) rs.row[rs.nrows++] = {pw, ncol, 0, s_xn2};
+    if (do_gn) rs.row[rs.nrows++] = {2 * pw, ncol, 1, s_gnorm};
+    return rs;
+}
+
+void Plan::epi_reduce(int ncol, int do_xn, int do_gn) {
+    if (nranks > 1) {
+        // one collective for the three scalars: the gnorm max travels as one
+        // slot per rank of a sum all-reduce and is folded after it
+        double *tail = d_Agg + NGMAX * NGMAX + NGMAX;
+        MMBA_HIP(hipMemsetAsync(tail, 0, sizeof(double) * (2 + nranks), s));
+        launch_reduce_multi(s, d_partial, epi_rows(pw, ncol, do_xn, do_gn, 0, 1, 2 + rank), tail);
+        allreduce(tail, 2 + nranks);
+        launch_fold_ranks(s, tail, nranks, d_scalar + SL_ZERO, do_xn, do_gn);
+        return;
+    }
+    const RedSpec rs = epi_rows(pw, ncol, do_xn, do_gn);
+    if (fl.sobs_ahead) {
+        // carried by the k_schur_obs enqueued with the Jacobian ahead of the
+        // decision (same rows: first = 0, gnorm)
+    } else if (red_defer_ok() && !timing) {  // rides in the next k_schur_init launch (C5)
+        pend_rs = rs;
+        fl.pend_red = true;
+    } else {
+        launch_reduce_multi(s, d_partial, rs, d_scalar);
+    }
+}
+
 void Plan::pre_jac_enqueue(const double *dx, double *eu, double *ed, const TrialRed &red) {
-    NeEpi epi;
-    epi.on = 1;
-    epi.first = 0;  // a later iteration: the first Jacobian is never enqueued ahead
-    epi.mode = opt.auto_param_scale == 1 ? 1 : 2;
-    epi.fnorm = 0.;
-    epi.fnorm_sq = d_scalar + SL_FNORM;  // the trial's ||f||^2 = the accepted fnorm^2
-    epi.do_xn = 0;
-    epi.do_gn = 1;
-    epi.x = dx;
-    epi.diag = d_diag;
-    epi.acnorm = d_acnorm;
-    epi.partial = d_partial;
-    epi.rstride = pw;
-    epi.cf_base = 0;
-    epi.bnd_base = ncf;
+    // what jac() passes at a later iteration (the first Jacobian is never
+    // enqueued ahead): gnorm from the trial's ||f||^2 = the accepted fnorm^2
+    const JacLM lm{0, opt.auto_param_scale == 1 ? 1 : 2, 0., d_scalar + SL_FNORM};
+    NeEpi epi = fused_epi(dx, lm);
     epi.gate = d_gate;
-    epi.probe = d_k2probe;
     // (red.on: k_jac_ne_u takes the decision itself and writes the gate the
     // launches behind it read; its ||f||^2 is its own SL_FNORM row value)
     launch_jac_ne(s, jb_recompute() ? P_nojb() : P, d_recs, d_step, opt.solver_type, d_J, d_jcol,
                   nloc_set ? nullptr : d_nloc, d_stale, eu, ed, d_Acc, d_g, epi, red);
     nloc_set = true;
-    pre_jac_pending = true;
+    fl.pre_jac_pending = true;
     // the bundle pass right behind it, under the same gate (round 6): the
     // GPU no longer idles between the two while the host takes its decision
-    // (the 5.8 us gap of profiles/r5_final6 / r6_k2).  jac() would launch
-    // it with this epilogue: the fused path's, at a later iteration (first
-    // = 0, gnorm from the device slot), with the lam = 0 bundle factor
-    pre_bnd_pending = false;
+    // (the 5.8 us gap of profiles/r5_final6 / r6_k2)
+    fl.pre_bnd_pending = false;
+    bool lb0 = false;
     if (P.nbs > 0 && P.JB != nullptr && nG == 0) {
-        if (jb_recompute()) {
-            epi.jb_recs = d_recs;
-            epi.jb_lmder = opt.solver_type == MMBA_SOLVER_CMINPACK_LMDER ? 1 : 0;
-        }
-        if (fold_ok && nB_solved > 0) {
-            epi.Lb = d_Lb;
-            epi.tb = d_tb;
-            epi.fail = d_fail;
-        }
+        epi_jb(*this, epi);
+        lb0 = epi_lb0(*this, epi);
         launch_ne(s, P, d_J, d_jcol, d_nloc, d_f, d_Acc, d_Acg, d_Abb, d_Abg, d_Agg, d_g,
                   d_glob_partial, glob_chunk, epi, true);
-        pre_bnd_pending = true;
+        fl.pre_bnd_pending = true;
     }
     // ... and (MMBA_PATH_PRE_SCHUR = 1) the next damped solve's first launch
     // (the undamped solve of the next lmpar: lam = 0 with the bundle factor
@@ -340,18 +420,14 @@ void Plan::pre_jac_enqueue(const double *dx, double *eu, double *ed, const Trial
     // before k_schur_obs to before k_schur_dest_u -- the host's launches of
     // the trial and the gated passes are what it waits for -- and the rate is
     // unchanged, so opt-in
-    pre_sobs_pending = false;
-    if (pre_bnd_pending && fold_ok && nB_solved > 0 && !rs_bnd && red_defer_ok() &&
+    fl.pre_sobs_pending = false;
+    if (fl.pre_bnd_pending && lb0 && !rs_bnd && red_defer_ok() &&
         path_choice(MMBA_PATH_PRE_SCHUR) == 1) {
-        const int ncol = ncf + (nB + NE_BND_TPB - 1) / NE_BND_TPB;
-        RedSpec rs{};
-        rs.flag_slot = -1;
-        rs.row[rs.nrows++] = {0, ncol, 1, SL_ZERO};
-        rs.row[rs.nrows++] = {2 * pw, ncol, 1, SL_GNORM};
+        const RedSpec rs = epi_rows(pw, epi_ncol(*this), epi.do_xn, epi.do_gn);
         launch_schur_obs(s, P, d_J, d_Lb, d_W, &rs, d_partial, d_scalar, d_gate);
-        pre_sobs_pending = true;
+        fl.pre_sobs_pending = true;
     }
-    pre_jac_x = dx;
+    fl.pre_jac_x = dx;
 }
 
 // The bundle records of the fused Jacobian pass re-evaluated by the bundle
@@ -411,65 +487,23 @@ void Plan::jac(const double *dx, const JacLM *lm) {
     // pass itself (k_jac_ne_u: J is written once and not re-read)
     const bool fuse = lm && ne_epilogue_fusable(P) && nrows == 0 && !b15;
     NeEpi epi;
-    if (fuse) {
-        epi.on = 1;
-        epi.first = lm->first;
-        epi.mode = lm->mode;
-        epi.fnorm = lm->fnorm;
-        epi.fnorm_sq = lm->fnorm_sq;
-        epi.do_xn = lm->first;
-        epi.do_gn = lm->fnorm_sq || lm->fnorm != 0.;
-        epi.x = dx;
-        epi.diag = d_diag;
-        epi.acnorm = d_acnorm;
-        epi.partial = d_partial;
-        epi.rstride = pw;
-        epi.cf_base = 0;
-        epi.bnd_base = ncf;
-    }
     epi.probe = d_k2probe;
-    if (fuse && path_choice(MMBA_PATH_NE_CF_SPLIT) != 0) {
-        // long camera-frame segments: the camera-frame normal equations over
-        // NE_CF_SPLIT workgroups each (k_ne_cf_split; launch_ne decides)
-        epi.cf_part = d_cf_part;
-        epi.cf_ticket = d_cf_ticket;
+    fl.lb0_valid = false;
+    if (fuse) {
+        epi = fused_epi(dx, *lm);
+        epi_cf_split(*this, epi);
+        fl.lb0_valid = epi_lb0(*this, epi);
     }
-    // unsharded plans with fast bundles: the bundle pass forms the lam = 0
-    // bundle factor the undamped solve reads next (no k_bundle_factor
-    // launch); with tail_reduce its last workgroup also reduces the
-    // epilogue rows
-    // (sharded too: every bundle a shard touches has all its observations
-    // there; the others have Abb = 0 and factor as the identity)
-    const bool fold = fuse && P.nbs > 0 && P.JB != nullptr && fold_ok;
-    const bool tail = fold && tail_reduce && nranks == 1;
-    lb0_valid = false;
-    if (tail) {
-        epi.fold = 1;
-        epi.scalar = d_scalar;
-        epi.ticket = d_mticket;
-        RedSpec &rf = epi.spec;
-        rf.flag_slot = -1;
-        const int ncol = ncf + (nB_solved > 0 ? (nB + NE_BND_TPB - 1) / NE_BND_TPB : 0);  // as below
-        rf.row[rf.nrows++] = {0, ncol, 1, SL_ZERO};
-        if (epi.do_xn) rf.row[rf.nrows++] = {pw, ncol, 0, SL_XN2};
-        if (epi.do_gn) rf.row[rf.nrows++] = {2 * pw, ncol, 1, SL_GNORM};
-    }
-    if (fold && nB_solved > 0) {
-        epi.Lb = d_Lb;
-        epi.tb = d_tb;
-        epi.fail = d_fail;
-        lb0_valid = true;
-    }
-    const bool k2_fused = !central && jac_ne_fusable(P, jac_ncv) && !k2_split;
-    const bool pre_done = pre_jac_pending && pre_jac_x == dx && k2_fused && fuse;
+    const bool k2_fused = !central && jac_ne_fusable(P, jac_ncv);
+    const bool pre_done = fl.pre_jac_pending && fl.pre_jac_x == dx && k2_fused && fuse;
     // sharded: g holds only this shard's terms -- zeroed BEFORE the fused
     // pass, which writes the camera-frame part of g itself
     if (nranks > 1) MMBA_HIP(hipMemsetAsync(d_g, 0, sizeof(double) * n, s));
-    pre_jac_pending = false;
-    const bool pre_bnd = pre_done && pre_bnd_pending;  // its bundle pass ran ahead too
-    pre_bnd_pending = false;
-    sobs_ahead = pre_done && pre_sobs_pending;  // and the next damped solve's k_schur_obs
-    pre_sobs_pending = false;
+    fl.pre_jac_pending = false;
+    const bool pre_bnd = pre_done && fl.pre_bnd_pending;  // its bundle pass ran ahead too
+    fl.pre_bnd_pending = false;
+    fl.sobs_ahead = pre_done && fl.pre_sobs_pending;  // and the next damped solve's k_schur_obs
+    fl.pre_sobs_pending = false;
     if (pre_done) {
         // k_jac_ne_u ran ahead at this x (its gate was open: the device took
         // this trial point, as the host did)
@@ -482,11 +516,7 @@ void Plan::jac(const double *dx, const JacLM *lm) {
         launch_jacobian(s, P, d_recs, d_ext_pert, d_step, opt.solver_type, d_J, d_jcol, d_nloc,
                         d_stale, d_eu, d_ed, jac_ncv, d_f, CB);
     }
-    if (k2_fused && jb_recompute()) {
-        // the bundle pass re-evaluates the records k_jac_ne_u did not store
-        epi.jb_recs = d_recs;
-        epi.jb_lmder = lmder ? 1 : 0;
-    }
+    if (k2_fused) epi_jb(*this, epi);
     launch_rows_jac(s, P, d_ext, d_ext_pert, d_step, central ? d_ext_pertB : nullptr,
                     central ? d_stepB : nullptr, lmder ? 1 : 0, d_Jrow, d_eu + 2 * (size_t)M,
                     n - 1);
@@ -498,32 +528,7 @@ void Plan::jac(const double *dx, const JacLM *lm) {
     if (nG > 0) allreduce(d_Agg, NGMAX * NGMAX + NGMAX);  // global block: all shards
     if (fuse) {
         span_end(SPAN_JAC);
-        const int ncol = ncf + (nB_solved > 0 ? (nB + NE_BND_TPB - 1) / NE_BND_TPB : 0);
-        RedSpec rs{};
-        rs.flag_slot = -1;
-        if (nranks > 1) {  // [ZERO, XN2, gnorm per rank]: one collective (see below)
-            double *tail = d_Agg + NGMAX * NGMAX + NGMAX;
-            MMBA_HIP(hipMemsetAsync(tail, 0, sizeof(double) * (2 + nranks), s));
-            rs.row[rs.nrows++] = {0, ncol, 1, 0};
-            if (epi.do_xn) rs.row[rs.nrows++] = {pw, ncol, 0, 1};
-            if (epi.do_gn) rs.row[rs.nrows++] = {2 * pw, ncol, 1, 2 + rank};
-            launch_reduce_multi(s, d_partial, rs, tail);
-            allreduce(tail, 2 + nranks);
-            launch_fold_ranks(s, tail, nranks, d_scalar + SL_ZERO, epi.do_xn, epi.do_gn);
-        } else if (!tail) {
-            rs.row[rs.nrows++] = {0, ncol, 1, SL_ZERO};
-            if (epi.do_xn) rs.row[rs.nrows++] = {pw, ncol, 0, SL_XN2};
-            if (epi.do_gn) rs.row[rs.nrows++] = {2 * pw, ncol, 1, SL_GNORM};
-            if (sobs_ahead) {
-                // carried by the k_schur_obs enqueued with the Jacobian ahead
-                // of the decision (same rows: first = 0, gnorm)
-            } else if (red_defer_ok() && !timing) {  // rides in the next k_schur_init launch
-                pend_rs = rs;
-                pend_red = true;
-            } else {
-                launch_reduce_multi(s, d_partial, rs, d_scalar);
-            }
-        }
+        epi_reduce(epi_ncol(*this), epi.do_xn, epi.do_gn);
     } else if (!lm) {
         launch_colnorms(s, P, d_Acc, d_Abb, d_Agg, d_acnorm, d_g);
         span_end(SPAN_JAC);
@@ -538,32 +543,32 @@ void Plan::jac(const double *dx, const JacLM *lm) {
                             nparts, pw, b15 ? d_c15 : nullptr, d_b15k + 4, d_g15, d_adiag15,
                             d_u15);
         span_end(SPAN_JAC);
-        RedSpec rs{};
-        rs.flag_slot = -1;
-        rs.row[rs.nrows++] = {0, nparts, 1, SL_ZERO};
-        if (do_xn) rs.row[rs.nrows++] = {pw, nparts, 0, SL_XN2};
-        if (do_gn) rs.row[rs.nrows++] = {2 * pw, nparts, 1, SL_GNORM};
-        if (nranks > 1) {
-            // one collective for the three scalars: the gnorm max travels as
-            // one slot per rank of a sum all-reduce and is folded after it
-            double *tail = d_Agg + NGMAX * NGMAX + NGMAX;
-            MMBA_HIP(hipMemsetAsync(tail, 0, sizeof(double) * (2 + nranks), s));
-            RedSpec rj{};
-            rj.flag_slot = -1;
-            rj.row[rj.nrows++] = {0, nparts, 1, 0};
-            if (do_xn) rj.row[rj.nrows++] = {pw, nparts, 0, 1};
-            if (do_gn) rj.row[rj.nrows++] = {2 * pw, nparts, 1, 2 + rank};
-            launch_reduce_multi(s, d_partial, rj, tail);
-            allreduce(tail, 2 + nranks);
-            launch_fold_ranks(s, tail, nranks, d_scalar + SL_ZERO, do_xn, do_gn);
-        } else if (red_defer_ok() && !timing) {  // rides in the next k_schur_init launch (C5)
-            pend_rs = rs;
-            pend_red = true;
-        } else {
-            launch_reduce_multi(s, d_partial, rs, d_scalar);
-        }
+        epi_reduce(nparts, do_xn, do_gn);
     }
     t_jac += wall_now() - t0;
+}
+
+// The trial point's parameter pass, wherever it rides (the damped solve's
+// back substitution, k_trial_prep_rec): the fields every plan's pass shares.
+static TrialFold trial_fold_base(const Plan &pl) {
+    TrialFold T;
+    T.x = pl.d_x;
+    T.diag = pl.d_diag;
+    T.wa1 = pl.d_wa1;
+    T.wa2 = pl.d_wa2;
+    T.wa3 = pl.d_wa3;
+    T.ext = pl.d_ext;
+    T.ext_pert = pl.d_ext_pert;
+    T.step = pl.d_step;
+    T.solver_type = pl.opt.solver_type;
+    T.delta = pl.opt.delta;
+    T.eps_dif = pl.fd_eps();
+    T.partial = pl.d_partial + 3 * (size_t)pl.pw;  // rows 3..6 (0..2: jac epilogue)
+    T.rstride = pl.pw;
+    T.own = pl.d_p_own;
+    T.recs = pl.d_recs;
+    T.brec = pl.d_brec;
+    return T;
 }
 
 // Trial point x + p, p = -xs (lmder): one parameter pass (step, norms,
@@ -578,26 +583,10 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
                        : trial_prep_rec ? trial_prep_rec_parts(P, n_prep_other)
                                         : nparts;
     if (!trial_folded && trial_prep_rec) {
-        TrialFold T;
-        T.x = d_x;
-        T.diag = d_diag;
-        T.wa1 = d_wa1;
-        T.wa2 = d_wa2;
-        T.wa3 = d_wa3;
-        T.ext = d_ext;
-        T.ext_pert = d_ext_pert;
-        T.step = d_step;
-        T.solver_type = opt.solver_type;
-        T.delta = opt.delta;
-        T.eps_dif = fd_eps();
+        TrialFold T = trial_fold_base(*this);
         T.other = d_prep_other;
         T.nother = n_prep_other;
-        T.partial = pr;
-        T.rstride = pw;
-        T.own = d_p_own;
         T.rec = 1;
-        T.recs = d_recs;
-        T.brec = d_brec;
         launch_trial_prep_rec(s, P, d_xs, T);
     } else if (!trial_folded) {
         launch_trial_prep(s, P, d_xs, d_x, d_diag, d_wa1, d_wa2, d_wa3, d_ext, d_ext_pert, d_step,
@@ -620,7 +609,7 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
     rs.row[rs.nrows++] = {6 * pw, trial_blocks(P), 0, SL_JP};
     // the fail flag: converted here, unless the back substitution did
     // (fail_early: SL_FAIL holds it and the flag is clear)
-    int *const flag = fill_dnorm && !fail_early ? d_fail : nullptr;
+    int *const flag = fill_dnorm && !fl.fail_early ? d_fail : nullptr;
     if (fill_dnorm) {  // the undamped solve's ||D xs||^2 and fail flag (solve_damped_enqueue)
         rs.row[rs.nrows++] = {3 * pw, tparts, 0, SL_DNORM};
         if (flag) rs.flag_slot = SL_FAIL;
@@ -628,22 +617,8 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
     // unsharded: the LM decision after this trial reads slots [0, SL_LAST],
     // which the reduction's last block mirrors to the host itself
     const bool mirror = host_mirror && nranks == 1;
-    // tail_reduce (unsharded, compiled out): the residual pass's last workgroup
-    // runs the reduction launch's work itself (RedTail: same rows, flag and
-    // mirror) -- off by default, see Plan::tail_reduce
-    RedTail T;
-    if (nranks == 1 && tail_reduce) {
-        T.on = 1;
-        T.spec = rs;
-        T.partial = d_partial;
-        T.scalar = d_scalar;
-        T.flag = flag;
-        T.host = mirror ? h_scalar : nullptr;
-        T.host_n = SL_LAST + 1;
-        T.ticket = d_mticket;
-    }
     launch_residual_jp(s, P, d_recs, d_ftrial, eu, ed, pr + 2 * (size_t)pw, d_J, d_jcol, d_nloc,
-                       b15 ? d_p15 : d_wa1, pr + 3 * (size_t)pw, d_dist_t, T);
+                       b15 ? d_p15 : d_wa1, pr + 3 * (size_t)pw, d_dist_t);
     span_end(SPAN_RESID);
     LmDec D;
     if (dec) {
@@ -670,8 +645,8 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
     // reduces in its own launch as before
     const bool hb_enq = dec && pre_hb_on && !b15;
     TrialRed R;
-    if (dec && jac_ahead && nranks == 1 && !b15 && mirror && seq_poll && !hb_enq && !timing &&
-        !T.on && !flag && trial_red_fold()) {
+    if (dec && jac_ahead && nranks == 1 && !b15 && mirror && !hb_enq && !timing && !flag &&
+        trial_red_fold()) {
         R.on = 1;
         R.spec = rs;
         R.dec = D;
@@ -681,26 +656,25 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
         R.host_n = SL_LAST + 1;
         R.host_seq = h_seq;
         R.seq = ++seq_next;
-        seq_pending = true;  // the mirror is pending on the Jacobian launch
+        fl.seq_pending = true;  // the mirror is pending on the Jacobian launch
         ++trial_red_folds;
-    } else if (!T.on) {
-        const bool sq = mirror && seq_poll;
-        if (sq) ++seq_next;
+    } else {
+        if (mirror) ++seq_next;
         launch_reduce_multi(s, d_partial, rs, d_scalar, flag, mirror ? h_scalar : nullptr,
-                            SL_LAST + 1, d_mticket, sq ? h_seq : nullptr, seq_next, D);
-        seq_pending = sq;
+                            SL_LAST + 1, d_mticket, mirror ? h_seq : nullptr, seq_next, D);
+        fl.seq_pending = mirror;
     }
     if (b15)  // ||J p||^2 of J = J_s + f c^T (no host mirror on these plans; rotated basis)
         launch_b15_jp(s, n, d_xs15r, d_g, d_c15r, d_b15k + 4, d_scalar + SL_JP);
-    mirror_pending = mirror;
-    pre_hb_enq = hb_enq;
-    if (pre_hb_enq)  // (the previous trial's kernel precedes it on s_hb[0]: no wait)
+    fl.mirror_pending = mirror;
+    fl.pre_hb_enq = hb_enq;
+    if (fl.pre_hb_enq)  // (the previous trial's kernel precedes it on s_hb[0]: no wait)
         MMBA_HIP(hipEventRecord(ev_hb[3], s));
     if (dec && jac_ahead) {  // the next Jacobian's first launch, gated on the device's decision
         stage_slots();
         pre_jac_enqueue(d_wa2, eu, ed, R);
     }
-    if (pre_hb_enq) {  // behind the decision, beside the gated Jacobian
+    if (fl.pre_hb_enq) {  // behind the decision, beside the gated Jacobian
         MMBA_HIP(hipStreamWaitEvent(s_hb[0], ev_hb[3], 0));
         launch_handback_host(s_hb[0], Mg, nrows, d_dev_of_ref, d_f, eu, ed, pre_hb_map[0],
                              pre_hb_map[1], pre_hb_map[2], d_scalar + SL_DGO, d_ftrial);
@@ -723,7 +697,7 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
         std::this_thread::sleep_for(std::chrono::milliseconds(2 * (long long)comm_timeout_ms()));
     }
     if (!red_defer_ok()) flush_red();
-    fail_early = false;
+    fl.fail_early = false;
     if (b15 && !b15_inner) {
         // B15: (M + U B U^T) xs = u + s c from M z_u = u and M z_c = c, the
         // same damped factorisation formed twice (the right-hand side rides
@@ -756,12 +730,12 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
     const double t0 = wall_now();
     trial_folded = false;
     // d_fail is zero here: launch_flag_to_scalar clears it after every use
-    if (band && bs.use_bd && nG == 0 && nranks == 1 && dnorm_slot >= 0) {
+    if (bd_one_launch() && dnorm_slot >= 0) {
         // the whole damped solve, ||D xs||^2 and the flag in one launch
         span_begin(SPAN_CHOL);
         bd_direct(s, P, bs.bd, d_Acc, d_g, d_diag, lam, d_xR, d_xs, d_fail, d_scalar, dnorm_slot,
-                  SL_FAIL, pend_red ? &pend_rs : nullptr, d_partial);
-        pend_red = false;
+                  SL_FAIL, fl.pend_red ? &pend_rs : nullptr, d_partial);
+        fl.pend_red = false;
         span_end(SPAN_CHOL);
         t_linear += wall_now() - t0;
         return;
@@ -770,22 +744,23 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
         // (folding the 3 x 3 factor into k_schur_obs, one factor per
         // observation, measured 34 us against 16 + 6 us: the per-observation
         // square roots and divisions lengthen the latency-bound pass)
-        if (!(lam == 0. && lb0_valid))  // else formed by the Jacobian's bundle pass
+        if (!(lam == 0. && fl.lb0_valid))  // else formed by the Jacobian's bundle pass
             launch_bundle_factor(s, P, d_Abb, d_Abg, d_g, d_diag, lam, d_Lb, d_tb, d_Wg, d_fail);
         // W of this undamped solve already enqueued behind the gated Jacobian
-        const bool ahead = sobs_ahead && lam == 0. && lb0_valid && !rs_bnd;
-        sobs_ahead = false;
-        lb0_valid = false;
+        const bool ahead = fl.sobs_ahead && lam == 0. && fl.lb0_valid && !rs_bnd;
+        fl.sobs_ahead = false;
+        fl.lb0_valid = false;
         if (rs_bnd)  // W rows of the virtual observations
             launch_schur_obs_rs(s, PV, M, d_nloc, d_vobs, d_vcoff, d_J, d_Lb, d_W);
         else if (!ahead) {
-            launch_schur_obs(s, P, d_J, d_Lb, d_W, pend_red ? &pend_rs : nullptr, d_partial,
+            launch_schur_obs(s, P, d_J, d_Lb, d_W, fl.pend_red ? &pend_rs : nullptr, d_partial,
                              d_scalar);
-            pend_red = false;
+            fl.pend_red = false;
         }
     }
     const DevProblem &PS = schur_problem();
     if (nR > 0) {
+        const Reduced kind = reduced_now();
         const SView V = sview();
         // unsharded, every rhs row is written by k_schur_init
         if (nranks > 1) MMBA_HIP(hipMemsetAsync(d_rhs, 0, sizeof(double) * nRpad, s));
@@ -795,14 +770,14 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
         // zeroed once at plan build; the partitioned path factors in place
         if (band && bs.red) {  // d_rhs is the tail of the block, zeroed above
             MMBA_HIP(hipMemsetAsync(bs.red, 0, sizeof(double) * (bs.red_count - nRpad), s));
-        } else if (band && ((!bs.use_bcr && !bs.use_bd) || rs_bnd)) {
+        } else if (band && ((!bs.use_bcr && kind != Reduced::BlockDiag) || rs_bnd)) {
             // (rolling shutter with solved bundles: k_rs_offdiag writes the
             // coupling blocks, so k_schur_dest subtracts instead of assigning)
             const int nb = nR - nG;
             MMBA_HIP(hipMemsetAsync(bs.Bd, 0, sizeof(double) * (size_t)nb * (bw + 1), s));
             if (nG > 0) MMBA_HIP(hipMemsetAsync(bs.Ga, 0, sizeof(double) * (size_t)nG * nb, s));
             MMBA_HIP(hipMemsetAsync(bs.Gd, 0, sizeof(double) * NGMAX * NGMAX, s));
-        } else if (dense) {
+        } else if (kind == Reduced::Dense) {
             MMBA_HIP(hipMemsetAsync(d_S, 0, sizeof(double) * (size_t)(nRpad + 1) * dld, s));
         } else if (!band) {
             MMBA_HIP(hipMemsetAsync(d_S, 0, sizeof(double) * (size_t)nslots * TILE * TILE, s));
@@ -810,8 +785,8 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
         const bool fold = fold_init && nB_solved > 0;
         if (!fold) {
             launch_schur_init(s, P, d_Acc, d_Acg, d_Agg, d_g, d_diag, lam, V, nRpad - nR, d_rhs,
-                              pend_red ? &pend_rs : nullptr, d_partial, d_scalar);
-            pend_red = false;
+                              fl.pend_red ? &pend_rs : nullptr, d_partial, d_scalar);
+            fl.pend_red = false;
         }
         flush_red();
         if (nB_solved > 0) {
@@ -838,44 +813,59 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
                                     s));
         }
         span_begin(SPAN_CHOL);
-        if (band && bs.use_bd) {  // factor, forward and backward
+        switch (kind) {
+        case Reduced::BlockDiag:  // factor, forward and backward
             bd_factor_solve(s, bs.bd, d_fail, d_rhs, d_yR, d_xR, d_xs);
-        } else if (band) {
+            break;
+        case Reduced::Pcr:  // the whole solve: x, scattered when unsharded
             if (bs.red) allreduce(bs.red, bs.red_count);
-            if (bs.use_pcr && !bs.df_off)  // the whole solve: x, scattered when unsharded
-                pcr_solve(s, bs.pcr, d_rhs, d_xR, bs.pcr.row_param ? d_xs : nullptr, d_fail);
-            else
-                band_factor_forward(s, bs, d_fail, d_probe, d_rhs, d_yR);
-        } else if (dense) {
+            pcr_solve(s, bs.pcr, d_rhs, d_xR, bs.pcr.row_param ? d_xs : nullptr, d_fail);
+            break;
+        case Reduced::Band:
+            if (bs.red) allreduce(bs.red, bs.red_count);
+            band_factor_forward(s, bs, d_fail, d_probe, d_rhs, d_yR);
+            break;
+        case Reduced::Dense:
             if (nranks > 1) {  // each shard's rows of S and r, summed (shard_dense)
                 allreduce(d_S, (size_t)ds.ld * (ds.n + 1));
                 allreduce(d_rhs, nRpad);
             }
             ds.factor_forward(s, d_rhs, d_yR, d_fail);  // y = L^-1 rhs rides along
-        } else {
+            break;
+        case Reduced::TiledNarrow:
+        case Reduced::Tiled:
             for (int k = 0; k < NT; ++k) {
                 const int r0 = panel_rows_off[k], nr = panel_rows_off[k + 1] - r0;
                 launch_chol_panel(s, d_S, d_slot, NT, k, d_rows + r0, nr, d_Linv, d_fail);
                 const int q0 = panel_pairs_off[k], nq = panel_pairs_off[k + 1] - q0;
                 launch_chol_update(s, d_S, d_slot, NT, k, d_pairs + q0, nq);
             }
+            break;
         }
         span_end(SPAN_CHOL);
-        if (band && bs.use_bd) {
-            // solved and scattered to parameter order above
-        } else if (band && bs.use_pcr && !bs.df_off) {
-            // solved by pcr_solve
-        } else if (band) {
+        bool scattered = false;  // the solver left the step in parameter order (d_xs) itself
+        switch (kind) {
+        case Reduced::BlockDiag:  // solved and scattered above
+            scattered = true;
+            break;
+        case Reduced::Pcr:  // solved by pcr_solve
+            scattered = bs.pcr.row_param != nullptr;
+            break;
+        case Reduced::Band:
             band_backward(s, bs, d_yR, d_xR);
             // every shard needs its halo camera-frame rows: each shard's own
             // rows [Ra, Rb) (and shard 0's arrow rows) all-gathered
             if (nranks > 1 && !bs.use_bcr) gather_step_rows();
-        } else if (dense) {
+            scattered = bs.use_bcr && bs.bcr.xs;  // the BCR backward solve
+            break;
+        case Reduced::Dense:
             ds.backward(s, d_yR, d_xR);
-        } else if (narrow) {
+            break;
+        case Reduced::TiledNarrow:
             launch_trsv_fwd_all(s, d_S, d_slot, NT, d_rows_off, d_rows, d_Linv, d_rhs, d_yR);
             launch_trsv_bwd_all(s, d_S, d_slot, NT, d_cols_off, d_cols, d_Linv, d_yR, d_xR);
-        } else {
+            break;
+        case Reduced::Tiled:
             for (int k = 0; k < NT; ++k) {
                 const int r0 = panel_rows_off[k], nr = panel_rows_off[k + 1] - r0;
                 launch_trsv_fwd(s, d_S, d_slot, NT, k, d_rows + r0, nr, d_Linv, d_rhs, d_yR);
@@ -884,12 +874,9 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
                 const int c0 = panel_cols_off[k], nc = panel_cols_off[k + 1] - c0;
                 launch_trsv_bwd(s, d_S, d_slot, NT, k, d_cols + c0, nc, d_Linv, d_yR, d_xR);
             }
+            break;
         }
-        // else done by the BCR backward solve / the block-diagonal back substitution
-        const bool pcr_now = band && bs.use_pcr && !bs.df_off;
-        if (!(band && ((bs.use_bcr && !pcr_now && bs.bcr.xs) || (pcr_now && bs.pcr.row_param) ||
-                       bs.use_bd)))
-            launch_scatter_xR(s, P, d_xR, d_xs);
+        if (!scattered) launch_scatter_xR(s, P, d_xR, d_xs);
     }
     trial_folded = false;
     if (nB_solved > 0) {
@@ -911,26 +898,10 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
             const bool group = !P.rs && !rs_bnd && (gpin < 0 ? kBacksubGroup : gpin == 1);
             const bool onepass = opin < 0 ? (group && kBacksubGroupOnepass) : opin == 1;
             if (!onepass) launch_obs_wtx(s, PS, d_W, d_xR, d_U);
-            TrialFold T;
-            T.x = d_x;
-            T.diag = d_diag;
-            T.wa1 = d_wa1;
-            T.wa2 = d_wa2;
-            T.wa3 = d_wa3;
-            T.ext = d_ext;
-            T.ext_pert = d_ext_pert;
-            T.step = d_step;
-            T.solver_type = opt.solver_type;
-            T.delta = opt.delta;
-            T.eps_dif = fd_eps();
+            TrialFold T = trial_fold_base(*this);
             T.other = d_trial_other;
             T.nother = n_trial_other;
-            T.partial = d_partial + 3 * (size_t)pw;
-            T.rstride = pw;
-            T.own = d_p_own;
             T.rec = trial_rec ? 1 : 0;
-            T.recs = d_recs;
-            T.brec = d_brec;
             T.group = group ? 1 : 0;
             T.bobs_rp = d_bobs_rp;
             T.brec_fwd = brec_fwd ? 1 : 0;
@@ -939,7 +910,7 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
                 // reduction: the deciders of k_jac_ne_u read the slot
                 T.flag = d_fail;
                 T.flag_out = d_scalar + SL_FAIL;
-                fail_early = true;
+                fl.fail_early = true;
             }
             launch_backsub_trial(s, PS, onepass ? d_W : nullptr, d_Wg, d_tb, d_Lb, d_xR, d_U, d_xs, T);
             trial_folded = true;
@@ -997,28 +968,36 @@ void Plan::newton_enqueue(double dxnorm) {
         launch_reduce_sum(s, d_usq, nB, d_scalar + SL_NEWT_B);
     }
     if (nR > 0) {
-        if (band && bs.use_pcr && !bs.df_off) {
+        const Reduced kind = reduced_now();
+        switch (kind) {
+        case Reduced::Pcr:
             // w^T S^-1 w (= ||L^-1 w||^2 of any Cholesky of S) from the last
             // solve's factors: per-block partials, summed in block order
             pcr_rhs_dot(s, bs.pcr, d_wR, d_ymask, d_fail);
             launch_reduce_sum(s, bs.pcr.part, bs.pcr.nblk, d_scalar + SL_NEWT_R);
-        } else if (band && bs.use_bd) {
+            break;
+        case Reduced::BlockDiag:
             bd_forward(s, bs.bd, d_wR, d_yR);
-        } else if (band) {
+            break;
+        case Reduced::Band:
             band_forward(s, bs, d_wR, d_yR);
-        } else if (dense) {
+            break;
+        case Reduced::Dense:
             ds.forward(s, d_wR, d_yR);
-        } else if (narrow) {
+            break;
+        case Reduced::TiledNarrow:
             launch_trsv_fwd_all(s, d_S, d_slot, NT, d_rows_off, d_rows, d_Linv, d_wR, d_yR);
-        } else {
+            break;
+        case Reduced::Tiled:
             for (int k = 0; k < NT; ++k) {
                 const int r0 = panel_rows_off[k], nr = panel_rows_off[k + 1] - r0;
                 launch_trsv_fwd(s, d_S, d_slot, NT, k, d_rows + r0, nr, d_Linv, d_wR, d_yR);
             }
+            break;
         }
-        if (band && bs.pcr_int && !bs.df_off)
+        if (sep_pcr_now())
             launch_sumsq_mix(s, d_yR, d_wR, nR, d_partial, nparts, d_scalar + SL_NEWT_R, d_ymask);
-        else if (!(band && bs.use_pcr && !bs.df_off))
+        else if (kind != Reduced::Pcr)
             launch_sumsq(s, d_yR, nullptr, nRpad, d_partial, nparts, d_scalar + SL_NEWT_R,
                          d_ymask, d_ticket);
     }
@@ -1047,8 +1026,8 @@ static void lmpar_first_enqueue(Plan &pl, bool defer = false, bool by_trial = fa
 struct PcrRestart {};
 static void check_newton(Plan &pl) {
     if (std::isfinite(pl.h_scalar[Plan::SL_NEWT_R])) return;
-    if (!(pl.band && (pl.bs.use_pcr || pl.bs.pcr_int)) || pl.bs.df_off) return;
-    pl.bs.df_off = true;
+    if (pl.reduced_now() != Plan::Reduced::Pcr && !pl.sep_pcr_now()) return;
+    pl.dataflow_off();
     launch_flag_to_scalar(pl.s, pl.d_fail, pl.d_scalar + Plan::SL_FAIL);
     throw PcrRestart{};
 }
@@ -1066,8 +1045,7 @@ static double lmpar_ne_once(Plan &pl, double delta, double *par, bool &pre, bool
         lmpar_first_enqueue(pl);
         pl.read_slots(Plan::SL_DNORM, Plan::SL_FAIL);
     }
-    if (h[Plan::SL_FAIL] >= 2. && !pl.bs.df_off) {
-        pl.bs.df_off = true;
+    if (h[Plan::SL_FAIL] >= 2. && pl.dataflow_off()) {
         pre = false;
         lmpar_first_enqueue(pl);
         pl.read_slots(Plan::SL_DNORM, Plan::SL_FAIL);
@@ -1109,10 +1087,9 @@ static double lmpar_ne_once(Plan &pl, double delta, double *par, bool &pre, bool
         // step.  Raise par (a larger damping is better conditioned) a few
         // times, then give up with an error.
         for (int retry = 0; h[Plan::SL_FAIL] != 0.; ++retry) {
-            if (h[Plan::SL_FAIL] >= 2. && !pl.bs.df_off) {
+            if (h[Plan::SL_FAIL] >= 2. && pl.dataflow_off()) {
                 // a timed-out dataflow wait (bit 2): the plan switches to the
                 // per-level launches for good and this damped solve runs again
-                pl.bs.df_off = true;
                 pl.solve_damped_enqueue(*par, Plan::SL_DNORM);
                 pl.read_slots(Plan::SL_DNORM, Plan::SL_FAIL);
                 continue;
@@ -1302,7 +1279,7 @@ int Plan::measure(const double *x, double *fvec_out, double *eu_out, double *ed_
     // an epilogue reduction a previous entry point deferred (pend_red) reads
     // d_partial rows this call rewrites: dropped, its slots are not read
     // outside the solve that deferred it
-    pend_red = false;
+    fl.pend_red = false;
     attrs_reset();
     if (x) {
         MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
@@ -1338,7 +1315,7 @@ int Plan::reproject(const double *x, double *point_out, double *marker_out) {
     // an epilogue reduction a previous entry point deferred (pend_red) reads
     // d_partial rows this call rewrites: dropped, its slots are not read
     // outside the solve that deferred it
-    pend_red = false;
+    fl.pend_red = false;
     attrs_reset();
     if (x) {
         MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
@@ -1358,7 +1335,7 @@ int Plan::dense_jacobian(const double *x, double *fjac) {
     // an epilogue reduction a previous entry point deferred (pend_red) reads
     // d_partial rows this call rewrites: dropped, its slots are not read
     // outside the solve that deferred it
-    pend_red = false;
+    fl.pend_red = false;
     if (nranks > 1) throw Unsupported{"dense Jacobian of a sharded plan"};
     attrs_reset();
     MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
@@ -1435,7 +1412,7 @@ int Plan::reduced_residual(const double *x, double lam, double *relres) {
     // an epilogue reduction a previous entry point deferred (pend_red) reads
     // d_partial rows this call rewrites: dropped, its slots are not read
     // outside the solve that deferred it
-    pend_red = false;
+    fl.pend_red = false;
     if (!dense) throw Unsupported{"reduced residual hook: dense reduced plans only"};
     if (!d_Skeep) {
         d_Skeep = dalloc<double>((size_t)ds.ld * (ds.n + 1));
@@ -1479,7 +1456,7 @@ int Plan::damped_step(const double *x, double lam, double *step_out, double *g_o
     if (fjac_out && P.jcol_implicit && !dbg_jcol_stored) {
         // uniform fast plans store no jcol (a property of the plan): one
         // Jacobian pass with it stored, ahead of the pass under test
-        pend_red = false;
+        fl.pend_red = false;
         attrs_reset();
         MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
         fun(d_x, d_f, d_eu, d_ed);
@@ -1496,7 +1473,7 @@ int Plan::damped_step(const double *x, double lam, double *step_out, double *g_o
     // an epilogue reduction a previous entry point deferred (pend_red) reads
     // d_partial rows this call rewrites: dropped, its slots are not read
     // outside the solve that deferred it
-    pend_red = false;
+    fl.pend_red = false;
     attrs_reset();
     MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
     MMBA_HIP(hipMemsetAsync(d_diag, 0, sizeof(double) * n, s));
@@ -1576,13 +1553,7 @@ int Plan::solve(double *x_inout, double *fvec_out, double *eu_out, double *ed_ou
     } catch (const SpecMismatch &) {
         host_sync();
         ++spec_replays;
-        pre_jac_pending = false;
-        pre_bnd_pending = false;
-        pre_sobs_pending = false;
-        sobs_ahead = false;
-        seq_pending = false;
-        mirror_pending = false;
-        slots_staged = false;
+        fl.reset();
         params_at = nullptr;
         recs_full_at = nullptr;
         const bool keep = pre_jac;
@@ -1601,15 +1572,14 @@ int Plan::solve(double *x_inout, double *fvec_out, double *eu_out, double *ed_ou
 
 int Plan::solve_once(double *x_inout, double *fvec_out, double *eu_out, double *ed_out,
                      mmba_result *res, const mmba_callbacks *cb, mmba_trace *trace) {
-    // an epilogue reduction a previous entry point deferred (pend_red) reads
-    // d_partial rows this call rewrites: dropped, its slots are not read
-    // outside the solve that deferred it
-    pend_red = false;
+    // nothing of an earlier entry point is in flight: an epilogue reduction
+    // it deferred (pend_red) reads d_partial rows this call rewrites and its
+    // slots are not read outside the solve that deferred it; every
+    // other flag is written by this solve's own enqueues before it is read
+    fl.reset();
     const double t_start = wall_now();
     t_func = t_jac = t_linear = 0.;
     cbk = cb;
-    pre_hb_enq = false;
-    pre_sobs_pending = sobs_ahead = false;
     pre_hb_on = nranks == 1 && n > 0 && pre_jac && (fvec_out || eu_out || ed_out) &&
                 path_choice(MMBA_PATH_PRE_HANDBACK) != 0 &&
                 map_outputs(fvec_out, eu_out, ed_out, pre_hb_map);
@@ -1626,18 +1596,17 @@ int Plan::solve_once(double *x_inout, double *fvec_out, double *eu_out, double *
     };
     // the host's decision on a trial point against the device's (LmDec):
     // a Jacobian the device ran ahead must be one the host takes
-    pre_jac_pending = false;
     auto settle_pre = [&](bool go_host) {
-        if (!pre_jac_pending) return;
+        if (!fl.pre_jac_pending) return;
         const bool go_dev = h_scalar[SL_DGO] != 0.;
         if (go_dev && !go_host) {
             // the Jacobian ran ahead at a trial point the host rejects (its
             // epilogue moved diag): replay the solve without speculation
-            pre_jac_pending = false;
+            fl.pre_jac_pending = false;
             throw SpecMismatch{};
         }
         // !go_dev: the gated launch did nothing (jac() launches it itself)
-        if (!go_dev || !go_host) pre_jac_pending = false;
+        if (!go_dev || !go_host) fl.pre_jac_pending = false;
     };
     // fresh attribute block (the scene's current values)
     attrs_reset();
@@ -1681,6 +1650,26 @@ int Plan::solve_once(double *x_inout, double *fvec_out, double *eu_out, double *
     bool f0_pending = false;  // x0's ||f||^2 is in SL_F0, not yet read
     bool x0_eval = false;     // x0's evaluation was enqueued
     double delta = 0., xnorm = 0., par = 0., fnorm = 0., gnorm = 0., ratio = 0.;
+    // the decision after a trial point as the device restates it (k_reduce_multi,
+    // k_jac_ne_u): the host's state before the trial
+    auto lm_dec = [&](int spec, bool first, bool f0, int nfev_trial) {
+        LmDec d;
+        d.spec = spec;
+        d.first = first;
+        d.f0 = f0;
+        d.fnorm = fnorm;
+        d.delta = delta;
+        d.xnorm = xnorm;
+        d.par = par;
+        d.gnorm = gnorm;
+        d.nfev = nfev_trial;
+        d.maxfev = maxfev;
+        d.factor = factor;
+        d.ftol = ftol;
+        d.xtol = xtol;
+        d.gtol = gtol;
+        return d;
+    };
 
     if (n <= 0 || mg < n || ftol < 0. || xtol < 0. || gtol < 0. || maxfev <= 0 || factor <= 0.)
         goto TERMINATE;
@@ -1771,7 +1760,7 @@ int Plan::solve_once(double *x_inout, double *fvec_out, double *eu_out, double *
             // ||D xs|| comes from the trial's ||D p|| reduction (no separate
             // norm launches), and sharded plans fold [DNORM, FAIL] into the
             // trial's all-reduce
-            const bool by_trial = spec && !(band && bs.use_bd && nG == 0 && nranks == 1) && !b15;
+            const bool by_trial = spec && !bd_one_launch() && !b15;
             lmpar_first_enqueue(*this, spec && nranks > 1, by_trial);
             // the next Jacobian is enqueued behind the trial, gated on the
             // device's restatement of the decision the host takes below
@@ -1779,23 +1768,7 @@ int Plan::solve_once(double *x_inout, double *fvec_out, double *eu_out, double *
             // the device's restatement of the decision: for the Jacobian
             // enqueued ahead (pj) and for the speculative hand-back
             const bool dv = pj || pre_hb_on;
-            LmDec dec;
-            if (dv) {
-                dec.spec = 1;
-                dec.first = iter == 1;
-                dec.f0 = f0_pending;
-                dec.fnorm = fnorm;
-                dec.delta = delta;
-                dec.xnorm = xnorm;
-                dec.par = par;
-                dec.gnorm = gnorm;
-                dec.nfev = nfev + 1;
-                dec.maxfev = maxfev;
-                dec.factor = factor;
-                dec.ftol = ftol;
-                dec.xtol = xtol;
-                dec.gtol = gtol;
-            }
+            const LmDec dec = lm_dec(1, iter == 1, f0_pending, nfev + 1);
             if (spec)
                 trial_enqueue(d_eu_s, d_ed_s, nranks > 1, by_trial, dv ? &dec : nullptr, pj);
             {
@@ -1841,22 +1814,8 @@ int Plan::solve_once(double *x_inout, double *fvec_out, double *eu_out, double *
                     std::swap(d_ed, d_ed_s);
                 } else {
                     settle_pre(false);  // a speculative trial lmpar did not take
-                    LmDec dec2;
-                    if (dv) {
-                        dec2.spec = 0;
-                        dec2.first = iter == 1;
-                        dec2.fnorm = fnorm;
-                        dec2.delta = delta;
-                        dec2.xnorm = xnorm;
-                        dec2.par = par;
-                        dec2.gnorm = gnorm;
-                        dec2.nfev = nfev;
-                        dec2.maxfev = maxfev;
-                        dec2.factor = factor;
-                        dec2.ftol = ftol;
-                        dec2.xtol = xtol;
-                        dec2.gtol = gtol;
-                    }
+                    // (f0 stays clear: x0's ||f|| was read with the first decision)
+                    const LmDec dec2 = lm_dec(0, iter == 1, false, nfev);
                     // trial point: ||D p||, f(x + p), ||J p|| and the
                     // candidate ||D x_new|| -- one synchronisation
                     trial_enqueue(d_eu, d_ed, false, false, dv ? &dec2 : nullptr, pj);
@@ -1954,7 +1913,7 @@ TERMINATE:
         const bool outs = fvec_out || eu_out || ed_out;
         // the speculative hand-back behind the last trial stored the lists
         // (the device decided the solve ends there: its info slot, mirrored)
-        const bool dev_handed = post_trial_end && pre_hb_enq && h_scalar[SL_DGO + 4] > 0.;
+        const bool dev_handed = post_trial_end && fl.pre_hb_enq && h_scalar[SL_DGO + 4] > 0.;
         if (dev_handed) ++pre_handbacks;
         if (staged && outs && !dev_handed)
             download_ref_order(d_f, d_eu, d_ed, fvec_out, eu_out, ed_out, false);

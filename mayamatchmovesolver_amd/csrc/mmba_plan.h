@@ -148,23 +148,9 @@ struct Plan {
     bool use_dest = false;
     int ndest = 0;
     int jac_ncv = 0;     // uniform fast Jacobian kernel (k_jacobian_u<jac_ncv>), 0: generic
-    // fixed choices of earlier A/B measurements (the alternatives stay in
-    // the source, compiled out): the fused Jacobian + normal-equation pass,
-    // the lam = 0 bundle factor formed in the bundle pass
-    static constexpr bool k2_split = false;
-    static constexpr bool fold_ok = true;
-    // reductions folded into their producers' last workgroup (one ticket
-    // counter) instead of a k_reduce_multi launch: measured slower on C4
-    // (k_residual<JP> 16.7 -> 30.5 us, k_ne_bnd_jb +7 us): 782 / 196 arrivals
-    // on one device-scope counter cost more than the launch they save (MI355X
-    // guide "fanin", ~12 ns per atomic)
-    static constexpr bool tail_reduce = false;
-    // page-locked sequence word of the mirrored reductions (read_slots
-    // polls it)
+    // page-locked sequence word of the mirrored reductions (read_slots polls it)
     unsigned *h_seq = nullptr;
     unsigned seq_next = 0;
-    bool seq_pending = false;  // the next mirrored read_slots polls h_seq
-    static constexpr bool seq_poll = true;  // (stream events: measured slower)
     int pc_uniform = 0;  // common block size of the solved camera-frames (0: mixed)
     int2 *d_dest = nullptr, *d_dpairs = nullptr;
     // destination lists of the split Schur pass (k_schur_dest_u over the
@@ -265,13 +251,11 @@ struct Plan {
     int *d_fail = nullptr;
     unsigned int *d_ticket = nullptr;  // single-launch reduction ticket (zero between uses)
     double *h_scalar = nullptr;  // pinned
-    // host mirror: trial reductions write slots [0, SL_LAST] straight
-    // into h_scalar (the last k_reduce_multi block) and read_slots skips its
-    // copy launch.  With a stream-event wait it measured 3 % slower per C4
-    // solve (round 2); with the page-locked sequence word the LM thread polls
-    // (seq_poll) it is 4 % faster (C4 14.48 -> 13.90 ms, profiles/r3_prejac)
-    unsigned *d_mticket = nullptr;
-    bool host_mirror = true, mirror_pending = false;
+    // host mirror: trial reductions write slots [0, SL_LAST] straight into
+    // h_scalar (the last k_reduce_multi block), read_slots skips its copy
+    // launch and polls the page-locked sequence word
+    unsigned *d_mticket = nullptr;  // k_reduce_multi's ticket
+    bool host_mirror = true;
     // every solved camera-frame has a diagonal Schur destination; fold_init:
     // k_schur_init rides in k_schur_dest_u (SchurInitFold)
     bool dest_diag_all = false, fold_init = false, dest_diag_ii = false;
@@ -363,6 +347,41 @@ struct Plan {
 
     void build(const mmba_problem *prob, const mmba_options *o);
 
+    // What a solve has in flight between its enqueue functions; cleared at
+    // the entry of solve_once and for the replay of a SpecMismatch solve.
+    struct InFlight {
+        // enqueued behind a trial at pre_jac_x, the host not yet decided: the
+        // next Jacobian's first launch, its bundle pass, the next k_schur_obs
+        bool pre_jac_pending = false, pre_bnd_pending = false, pre_sobs_pending = false;
+        const double *pre_jac_x = nullptr;
+        // the jac() that took the pre-enqueued pass hands its k_schur_obs to
+        // the next damped solve, which then skips that launch
+        bool sobs_ahead = false;
+        bool seq_pending = false;     // the next mirrored read_slots polls h_seq
+        bool mirror_pending = false;  // the last trial's reduction mirrors its slots
+        // the trial's slots staged (D2H copy unless mirrored, then an event)
+        // before the pre-enqueued Jacobian: read_slots(0, SL_LAST) only waits
+        bool slots_staged = false;
+        bool pre_hb_enq = false;  // k_handback_host enqueued behind the last trial
+        // d_Lb / d_tb hold the lam = 0 bundle factor of the current normal
+        // equations (NeEpi::Lb): the next undamped solve launches no k_bundle_factor
+        bool lb0_valid = false;
+        // the last back substitution converted the factorisation flag to
+        // SL_FAIL (TrialFold::flag): the trial's reduction leaves both alone
+        bool fail_early = false;
+        // the Jacobian epilogue's rows (pend_rs) held back for the next damped
+        // solve's first launch (C5); flush_red launches them alone otherwise
+        bool pend_red = false;
+        void reset() { *this = InFlight(); }
+    } fl;
+    // The reduced solver in use, from band / bs / dense / narrow.  Evaluated
+    // at every use: a timed-out dataflow wait moves Pcr to Band in mid-solve.
+    enum class Reduced { BlockDiag, Pcr, Band, Dense, TiledNarrow, Tiled };
+    Reduced reduced_now() const;
+    bool bd_one_launch() const;  // bd_direct: solve, step norm and flag in one launch
+    bool sep_pcr_now() const;    // the separator form's interiors by cyclic reduction
+    bool dataflow_off();         // switches for good; false: had switched already
+
     // LM building blocks.  *_enqueue functions only launch work; results land
     // in device scalar slots (all-reduced across shards) and are fetched with
     // one read_slots() per decision point of the MINPACK control flow.
@@ -407,7 +426,6 @@ struct Plan {
         NSLOT = 28
     };
     void read_slots(int lo, int hi);
-    static constexpr bool spin_wait = true;  // (blocking synchronisation: slower)
     hipEvent_t ev_sync = nullptr;  // [lo, hi] inclusive, one D2H copy + sync
     double read_scalar(int slot = 0);
     void stream_wait();
@@ -437,6 +455,12 @@ struct Plan {
         const double *fnorm_sq = nullptr;
     };
     void jac(const double *dx, const JacLM *lm = nullptr);
+    // The fused epilogue of the Jacobian at dx, for jac() and for the launches
+    // pre_jac_enqueue makes in its place
+    NeEpi fused_epi(const double *dx, const JacLM &lm) const;
+    // the epilogue's rows (ncol partials each) to SL_ZERO, SL_XN2, SL_GNORM:
+    // one collective, a launch ahead or behind, or a launch of their own
+    void epi_reduce(int ncol, int do_xn, int do_gn);
     // interrupt polls of the reference (MComputation::isInterruptRequested):
     // true once the caller's callback asks to stop
     const mmba_callbacks *cbk = nullptr;
@@ -454,11 +478,6 @@ struct Plan {
     // flag SL_FAIL of the undamped solve enqueued with dnorm_by_trial
     void trial_enqueue(double *eu, double *ed, bool with_dnorm = false, bool fill_dnorm = false,
                        const LmDec *dec = nullptr, bool jac_ahead = false);
-    // The next Jacobian's first launch (k_jac_ne_u at the trial point),
-    // enqueued behind a trial whose reduction restates the host's decision
-    // (LmDec): it runs only when that decision takes the trial and goes on,
-    // so the GPU starts the next iteration while the host reads the trial.
-    // (cleared for the replay of a SpecMismatch solve)
     // the trial point's parameter pass fused into the bundle back
     // substitution of the damped solve (launch_backsub_trial);
     // otherwise k_trial_prep
@@ -483,9 +502,11 @@ struct Plan {
     int n_prep_other = 0;
     int *d_trial_other = nullptr;
     int n_trial_other = 0;
-    bool pre_jac = true;
-    bool pre_jac_pending = false;   // enqueued, the host has not decided yet
-    const double *pre_jac_x = nullptr;
+    // The next Jacobian's first launch (k_jac_ne_u at the trial point),
+    // enqueued behind a trial whose reduction restates the host's decision
+    // (LmDec): it runs only when that decision takes the trial and goes on,
+    // so the GPU starts the next iteration while the host reads the trial.
+    bool pre_jac = true;  // (cleared for the replay of a SpecMismatch solve)
     int *d_gate = nullptr;
     bool pre_jac_ok() const;
     // red (MMBA_PATH_TRIAL_RED_FOLD): the trial's reduction, decision and
@@ -496,34 +517,16 @@ struct Plan {
     // Unpinned choice of MMBA_PATH_TRIAL_RED_FOLD
     static constexpr bool kTrialRedFold = true;
     bool trial_red_fold() const;
-    // the last damped solve's back substitution converted the factorisation
-    // flag to SL_FAIL and cleared it (TrialFold::flag): the trial's reduction
-    // leaves both alone
-    bool fail_early = false;
-    // the trial's slots staged (D2H copy unless mirrored, then an event)
-    // before the pre-enqueued Jacobian: read_slots(0, SL_LAST) only waits
-    bool slots_staged = false;
     void stage_slots();
-    // the Jacobian epilogue's row reductions held back for the next damped
-    // solve's k_schur_init launch (block diagonal + arrow plans without a
-    // solved bundle, C5); flush_red launches them alone wherever anything
-    // else comes first
-    bool pend_red = false;
-    RedSpec pend_rs{};
+    RedSpec pend_rs{};  // the rows of InFlight::pend_red
     bool red_defer_ok() const;
     void flush_red();
     void host_sync();
     bool jb_recompute() const;
     DevProblem P_nojb() const;
     bool stall_done = false;  // MMBA_PATH_STALL_SHARD fired
-    bool pre_bnd_pending = false;
-    // k_schur_obs enqueued behind the gated bundle pass too, with the
-    // Jacobian epilogue's deferred reduction (pre_jac_enqueue); sobs_ahead:
-    // the jac() that took the pre-enqueued pass hands it to the next damped
-    // solve, which then skips that launch
-    bool pre_sobs_pending = false, sobs_ahead = false;
     double *d_cf_part = nullptr;      // k_ne_cf_split partial sums
-    unsigned *d_cf_ticket = nullptr;  // k_ne_cf_split tickets (monotonic)  // the bundle pass was enqueued with the pre-enqueued Jacobian
+    unsigned *d_cf_ticket = nullptr;  // k_ne_cf_split tickets (monotonic)
     void wait_event();
     // speculative trial (lmpar's first, undamped, step taken before the
     // host has read it): its errorList / errorDistanceList land here and are
@@ -541,10 +544,6 @@ struct Plan {
     // d_brec hold: an evaluation or trial point builds the full set in its
     // one records launch, so the Jacobian at an accepted point needs none
     const double *recs_full_at = nullptr;
-    // d_Lb / d_tb hold the bundle factor at lam = 0 of the current normal
-    // equations, formed by the Jacobian's bundle pass (NeEpi::Lb); the next
-    // undamped solve uses it instead of launching k_bundle_factor
-    bool lb0_valid = false;
     void records_enqueue(const double *xat, int base_only);
     void attrs_reset() {  // the scene's own attribute values
         MMBA_HIP(hipMemcpyAsync(P.attr_val, d_attr0, attr_bytes, hipMemcpyDeviceToDevice, s));
@@ -621,7 +620,7 @@ struct Plan {
     // gated on it, so the lists leave as soon as the device has decided the
     // solve ends there; the host skips its own hand-back when it ends on
     // that trial and the device's slots say the kernel stored them
-    bool pre_hb_on = false, pre_hb_enq = false;
+    bool pre_hb_on = false;
     long long pre_handbacks = 0;  // solves whose lists the speculative hand-back stored
     long long ne_split_launches = 0;  // k_ne_cf_split launches (launch_ne took the split branch)
     long long trial_red_folds = 0;    // trials reduced and decided inside k_jac_ne_u (TrialRed)
