@@ -774,8 +774,15 @@ int mmba_debug_reduced_residual(mmba_plan *plan, const double *x, double lam, do
  * solver and back substitution.  Outputs (each may be NULL), in parameter
  * order: step_out [n] = p, g_out [n] = J^T f, diag_out [n] = D, and fjac_out
  * [m x n, column-major] = the dense J reassembled after the solve from what
- * the pass stored.  MMBA_ERR_INVALID when the factorisation fails;
- * MMBA_ERR_UNSUPPORTED for sharded, multi-device and B15 plans. */
+ * the pass stored.  MMBA_ERR_INVALID when the factorisation fails (on every
+ * shard together); MMBA_ERR_UNSUPPORTED for B15 plans.
+ * A sharded plan runs the same calls with the solve's collectives, so every
+ * shard calls together.  step_out, g_out and diag_out are whole on every
+ * rank (each parameter's entry from its owner, all-gathered).  fjac_out
+ * [mg x n, all residuals] holds only the rows of the shard's own
+ * observations (the attribute rows on rank 0) and zeros elsewhere: the
+ * shards' arrays sum to J.  A multi-device plan runs its shards in the one
+ * call; each writes its own entries and rows into the caller's arrays. */
 int mmba_debug_damped_step(mmba_plan *plan, const double *x, double lam, double *step_out,
                            double *g_out, double *diag_out, double *fjac_out);
 

@@ -546,10 +546,8 @@ int mmba_debug_reduced_residual(mmba_plan *plan, const double *x, double lam, do
 int mmba_debug_damped_step(mmba_plan *plan, const double *x, double lam, double *step_out,
                            double *g_out, double *diag_out, double *fjac_out) {
     if (!plan || !x || !(lam >= 0.)) return MMBA_ERR_INVALID;
-    if (plan->group) {
-        set_error("unsupported: damped step hook on a multi-device plan");
-        return MMBA_ERR_UNSUPPORTED;
-    }
+    if (plan->group)
+        return group_debug_damped_step(plan, x, lam, step_out, g_out, diag_out, fjac_out);
     MMBA_GUARD({
         Plan &p = plan->impl;
         MMBA_HIP(hipSetDevice(p.ctx->device));

@@ -246,6 +246,47 @@ void Plan::handback_sharded(const double *dx, double *x_out, double *f_out, doub
     host_sync();
 }
 
+// The damped-step hook's vectors (d_xs, d_g, d_diag) to the caller, as
+// handback_sharded returns x: every parameter's entry from its owner.  An
+// owner's entries are complete -- camera-frame blocks by the frame partition
+// (every observation of an own camera-frame is an own observation), bundle
+// blocks through the halo (the owner holds every observation of its bundles),
+// globals through the d_Agg all-reduce (identical on every shard; rank 0's
+// are taken) -- so nothing is summed here.  Group shards write their own
+// entries into the caller's arrays; otherwise one all-gather and every rank
+// returns the whole vectors.
+void Plan::handback_step(double *step_out, double *g_out, double *diag_out) {
+    const size_t count = 3 * (size_t)npar_pad;
+    if (!d_dbg_pack) d_dbg_pack = dalloc<double>(count * (1 + (size_t)nranks) + 3 * (size_t)n);
+    double *pack = d_dbg_pack, *all = pack + count, *full = all + count * nranks;
+    const double *src[3] = {d_xs, d_g, d_diag};
+    double *dst[3] = {step_out, g_out, diag_out};
+    for (int j = 0; j < 3; ++j)
+        k_own_pack<<<nblk(npar_pad, 256), 256, 0, s>>>(n_own, npar_pad, d_own_par, src[j], 0, 0,
+                                                      nullptr, nullptr, nullptr, nullptr,
+                                                      pack + (size_t)j * npar_pad);
+    if (host_gather) {
+        std::vector<double> h(count);
+        MMBA_HIP(hipMemcpyAsync(h.data(), pack, sizeof(double) * count, hipMemcpyDeviceToHost, s));
+        host_sync();
+        for (int j = 0; j < 3; ++j)
+            if (dst[j])
+                for (int i = 0; i < n_own; ++i)
+                    dst[j][own_par_h[i]] = h[(size_t)j * npar_pad + i];
+        return;
+    }
+    comm->allgather(pack, all, count, s);
+    for (int j = 0; j < 3; ++j) {
+        k_own_unpack<<<dim3(nblk(npar_pad, 256), nranks), 256, 0, s>>>(
+            nranks, count, all + (size_t)j * npar_pad, npar_pad, d_own_par_all,
+            full + (size_t)j * n, 0, nullptr, nullptr, nullptr, nullptr);
+        if (dst[j])
+            MMBA_HIP(hipMemcpyAsync(dst[j], full + (size_t)j * n, sizeof(double) * n,
+                                    hipMemcpyDeviceToHost, s));
+    }
+    host_sync();
+}
+
 bool Plan::poll_agree() {
     if (!pshare) return poll_interrupt();
     const int v = rank == 0 ? (poll_interrupt() ? 1 : 0) : 0;
@@ -508,6 +549,22 @@ int group_plan_jacobian(mmba_plan *plan, const double *x, double *fjac) {
         return MMBA_ERR_UNSUPPORTED;
     }
     return mmba_plan_jacobian(g.plans[0], x, fjac);
+}
+
+// every shard writes its own parameters' entries and its own observations'
+// rows of J into the caller's arrays; fjac_out is cleared here, once, before
+// the shards start
+int group_debug_damped_step(mmba_plan *plan, const double *x, double lam, double *step_out,
+                            double *g_out, double *diag_out, double *fjac_out) {
+    ShardGroup &g = *plan->group;
+    if (g.n > 1 && fjac_out) {
+        const Plan &p0 = g.plans[0]->impl;
+        std::memset(fjac_out, 0, sizeof(double) * (size_t)p0.mg * p0.n);
+    }
+    const std::function<int(int)> f = [&](int k) -> int {
+        return mmba_debug_damped_step(g.plans[k], x, lam, step_out, g_out, diag_out, fjac_out);
+    };
+    return g.run(f);
 }
 
 int group_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,

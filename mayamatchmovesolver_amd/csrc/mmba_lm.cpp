@@ -1348,9 +1348,13 @@ int Plan::dense_jacobian(const double *x, double *fjac) {
     return MMBA_OK;
 }
 
-// The dense reference-order Jacobian (column-major, ldfjac = m) from what the
+// The dense reference-order Jacobian (column-major, ldfjac = mg) from what the
 // last Jacobian pass stored: d_J / d_jcol / d_nloc and the attribute rows.
-void Plan::assemble_dense_jacobian(double *fjac) {
+// own_rows (a sharded plan): only the rows of this shard's own observations
+// (a halo observation's rows are its owner's) and, on rank 0, the attribute
+// rows, so the shards' arrays sum to the whole J; a group shard writes them
+// into the caller's array, which the caller cleared.
+void Plan::assemble_dense_jacobian(double *fjac, bool own_rows) {
     std::vector<double> J((size_t)2 * P.lmax * M), Jr(nrows);
     std::vector<int> jc((size_t)std::max(P.lmax, 1) * M), nl(M), rp(nrows);
     if (nrows > 0) {
@@ -1365,17 +1369,25 @@ void Plan::assemble_dense_jacobian(double *fjac) {
     MMBA_HIP(hipMemcpyAsync(nl.data(), d_nloc, sizeof(int) * M, hipMemcpyDeviceToHost, s));
     host_sync();
     collect_spans();
-    std::memset(fjac, 0, sizeof(double) * (size_t)m * n);
+    const size_t ld = (size_t)mg;
+    std::vector<char> own;
+    if (own_rows) {
+        own.assign(Mg, 0);
+        for (int r : own_ref_h) own[r] = 1;
+    }
+    if (!(own_rows && host_gather)) std::memset(fjac, 0, sizeof(double) * ld * n);
     for (int i = 0; i < M; ++i) {
         const int r = ref_of_dev[i];
+        if (own_rows && !own[r]) continue;
         for (int l = 0; l < nl[i]; ++l) {
             const int p = jc[(size_t)l * M + i];
-            fjac[(size_t)p * m + 2 * r] = J[(size_t)(2 * l) * M + i];
-            fjac[(size_t)p * m + 2 * r + 1] = J[(size_t)(2 * l + 1) * M + i];
+            fjac[(size_t)p * ld + 2 * r] = J[(size_t)(2 * l) * M + i];
+            fjac[(size_t)p * ld + 2 * r + 1] = J[(size_t)(2 * l + 1) * M + i];
         }
     }
-    for (int r = 0; r < nrows; ++r)
-        if (rp[r] >= 0) fjac[(size_t)rp[r] * m + 2 * (size_t)M + r] = Jr[r];
+    if (!own_rows || rank == 0)
+        for (int r = 0; r < nrows; ++r)
+            if (rp[r] >= 0) fjac[(size_t)rp[r] * ld + 2 * (size_t)Mg + r] = Jr[r];
     if (b15) {  // J = J_s + f c^T
         std::vector<double> c(n), f(2 * (size_t)M);
         MMBA_HIP(hipMemcpy(c.data(), d_c15, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -1384,8 +1396,8 @@ void Plan::assemble_dense_jacobian(double *fjac) {
             if (c[p] == 0.) continue;
             for (int i = 0; i < M; ++i) {
                 const int r = ref_of_dev[i];
-                fjac[(size_t)p * m + 2 * r] += f[2 * (size_t)i] * c[p];
-                fjac[(size_t)p * m + 2 * r + 1] += f[2 * (size_t)i + 1] * c[p];
+                fjac[(size_t)p * ld + 2 * r] += f[2 * (size_t)i] * c[p];
+                fjac[(size_t)p * ld + 2 * r + 1] += f[2 * (size_t)i + 1] * c[p];
             }
         }
     }
@@ -1449,25 +1461,41 @@ int Plan::reduced_residual(const double *x, double lam, double *relres) {
 // as a solve's first iteration runs it -- evaluation, Jacobian pass with the
 // lmder bookkeeping (first = 1, mode = 1: D = column norms), damped solve --
 // then the step, g, D and the dense J the pass stored, in parameter order.
+// A sharded plan runs the same calls with the solve's collectives (every
+// shard calls together); each shard hands back its own parameters' entries
+// and its own observations' rows (Plan::handback_step).
 int Plan::damped_step(const double *x, double lam, double *step_out, double *g_out,
                       double *diag_out, double *fjac_out) {
-    if (nranks > 1) throw Unsupported{"damped step hook: sharded plan"};
     if (b15) throw Unsupported{"damped step hook: B15 plan"};
-    if (fjac_out && P.jcol_implicit && !dbg_jcol_stored) {
-        // uniform fast plans store no jcol (a property of the plan): one
-        // Jacobian pass with it stored, ahead of the pass under test
+    const bool sharded = nranks > 1;
+    // uniform fast plans store no jcol (a property of the plan): one
+    // Jacobian pass with it stored, ahead of the pass under test
+    bool pre = fjac_out && P.jcol_implicit && !dbg_jcol_stored;
+    if (sharded) {
+        // the pre-pass carries collectives (the evaluation's ||f||^2, the
+        // global block): every shard takes it when any shard needs it
+        if (!d_dbg_flag) d_dbg_flag = dalloc<double>(1);
+        double v = pre ? 1. : 0.;
+        MMBA_HIP(hipMemcpyAsync(d_dbg_flag, &v, sizeof(double), hipMemcpyHostToDevice, s));
+        allreduce(d_dbg_flag, 1, ReduceOp::Max);
+        MMBA_HIP(hipMemcpyAsync(&v, d_dbg_flag, sizeof(double), hipMemcpyDeviceToHost, s));
+        host_sync();
+        pre = v != 0.;
+    }
+    if (pre) {
         fl.pend_red = false;
         attrs_reset();
         MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
         fun(d_x, d_f, d_eu, d_ed);
+        const int implicit = P.jcol_implicit;
         P.jcol_implicit = 0;
         try {
             jac(d_x);
         } catch (...) {
-            P.jcol_implicit = 1;
+            P.jcol_implicit = implicit;
             throw;
         }
-        P.jcol_implicit = 1;
+        P.jcol_implicit = implicit;
         dbg_jcol_stored = true;
     }
     // an epilogue reduction a previous entry point deferred (pend_red) reads
@@ -1482,15 +1510,22 @@ int Plan::damped_step(const double *x, double lam, double *step_out, double *g_o
     jac(d_x, &lm);
     solve_damped_enqueue(lam, SL_DNORM);
     read_slots(SL_DNORM, SL_FAIL);
+    // (sharded: the flag is all-reduced, every shard leaves here together)
     if (h_scalar[SL_FAIL] != 0.) throw Invalid{"damped step hook: the factorisation failed"};
-    if (step_out)
-        MMBA_HIP(hipMemcpyAsync(step_out, d_xs, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (g_out) MMBA_HIP(hipMemcpyAsync(g_out, d_g, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    if (diag_out)
-        MMBA_HIP(hipMemcpyAsync(diag_out, d_diag, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    host_sync();
-    if (fjac_out)
-        assemble_dense_jacobian(fjac_out);  // after the solve: what the pass itself stored
+    if (sharded) {
+        handback_step(step_out, g_out, diag_out);
+    } else {
+        if (step_out)
+            MMBA_HIP(hipMemcpyAsync(step_out, d_xs, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+        if (g_out)
+            MMBA_HIP(hipMemcpyAsync(g_out, d_g, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+        if (diag_out)
+            MMBA_HIP(hipMemcpyAsync(diag_out, d_diag, sizeof(double) * n, hipMemcpyDeviceToHost,
+                                    s));
+        host_sync();
+    }
+    if (fjac_out)  // after the solve: what the pass itself stored
+        assemble_dense_jacobian(fjac_out, sharded);
     else
         collect_spans();
     return MMBA_OK;

@@ -591,7 +591,12 @@ struct Plan {
     // test hook (mmba_debug_damped_step): the damped step of one LM iteration
     // at x, with g, D and the dense J its Jacobian pass stored
     bool dbg_jcol_stored = false;  // d_jcol filled for a plan that leaves it implicit
-    void assemble_dense_jacobian(double *fjac);
+    double *d_dbg_flag = nullptr;  // sharded: "a shard needs the jcol pre-pass", max-reduced
+    // sharded hand-back of the hook (mmba_group.cpp): scratch of its own,
+    // [3 npar_pad | 3 npar_pad nranks | 3 n]; d_g and d_diag are only read
+    double *d_dbg_pack = nullptr;
+    void handback_step(double *step_out, double *g_out, double *diag_out);
+    void assemble_dense_jacobian(double *fjac, bool own_rows = false);
     int damped_step(const double *x, double lam, double *step_out, double *g_out,
                     double *diag_out, double *fjac_out);
     int reproject(const double *x, double *point_out, double *marker_out);
@@ -650,6 +655,8 @@ int group_plan_measure(mmba_plan *plan, const double *x, double *fvec_out, doubl
 int group_plan_reproject(mmba_plan *plan, const double *x, double *point_xy_out,
                          double *marker_xy_out);
 int group_plan_jacobian(mmba_plan *plan, const double *x, double *fjac);
+int group_debug_damped_step(mmba_plan *plan, const double *x, double lam, double *step_out,
+                            double *g_out, double *diag_out, double *fjac_out);
 int group_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,
                        double *err_dist_out);
 int group_plan_set_attr_values(mmba_plan *plan, const double *attr_values);

@@ -32,8 +32,19 @@ cannot pass silently.
 
 Pairs left out (lam = 0 only), by name, in LEFT_OUT with their e64.
 
+Sharded and group plans: test_gpu_damped_step_sharded.py, the same reference
+and bars.
+
 Not reached: k_schur_pairs (Plan::build takes it only above 2^30 destination
-pairs) and sharded, group, per-frame-batch, central and B15 plans.
+pairs);
+  B15 plans: the hook refuses them -- the rotated basis and the Woodbury term
+    need a reference formulation of their own.  Central differences are among
+    them: with lmder every scene whose animated parameters span several
+    frames builds a B15 plan or none (Plan::build), the C4 and C2 windows of
+    test_gpu_b15.py included (test_gpu_damped_step_sharded.py asserts the
+    refusal), and lmdif has forward differences only;
+  per-frame batch plans: mmba_plan_solve_per_frame runs its own batched LM
+    (mmba_batch.hip), which has no single damped step to hand back.
 
 Measured on an MI355X, e64 / the device's error (the step measure, on the
 device's J; g and D stayed below 1.1e-3 of their bars everywhere; every run

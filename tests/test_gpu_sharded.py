@@ -15,23 +15,28 @@ from mayamatchmovesolver_amd.solver import Comm, Context, Solver
 pytestmark = pytest.mark.gpu
 
 
-def run_sharded(prob, opt, n, replicated=None, band_solver=None):
+def run_sharded(prob, opt, n, replicated=None, band_solver=None, call=None, stats=None):
     """Solve on n in-process shards.  replicated (list): receives each shard's
     shards_replicated statistic (1: the problem did not shard and every shard
     solved all of it, mmba_plan_create_sharded); band_solver (list): each
-    shard's band_solver statistic (4: the separator form)."""
+    shard's band_solver statistic (4: the separator form); stats (list): each
+    shard's whole kernel_stats.  call: run on each shard's Solver, on the
+    shard's thread, instead of solve() (collective entry points: every
+    shard's call must make the same ones); its value is the shard's output."""
     comms = Comm.local_group(n)
     ctxs = [Context(0) for _ in range(n)]
     outs, errs, reps, bsol = [None] * n, [None] * n, [None] * n, [None] * n
+    sts = [None] * n
 
     def work(r):
         try:
             s = Solver(prob, opt, context=ctxs[r], comm=comms[r])
             try:
                 st = s.kernel_stats()
+                sts[r] = st
                 reps[r] = st["shards_replicated"]
                 bsol[r] = st["band_solver"]
-                outs[r] = s.solve()
+                outs[r] = s.solve() if call is None else call(s)
             finally:
                 s.close()
         except Exception as e:  # noqa: BLE001 - reported below
@@ -52,6 +57,8 @@ def run_sharded(prob, opt, n, replicated=None, band_solver=None):
         replicated[:] = reps
     if band_solver is not None:
         band_solver[:] = bsol
+    if stats is not None:
+        stats[:] = sts
     return outs
 
 
