@@ -535,6 +535,50 @@ int mmba_plan_solve(mmba_plan *plan, double *x_inout, double *fvec_out,
 int mmba_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,
                       double *err_dist_out);
 
+/* Per-frame and per-marker deviation metrics of the plan's last
+ * mmba_plan_solve / mmba_plan_measure, reduced on the device from the
+ * errorDistanceList kept in HBM -- the list mmba_plan_outputs would hand back
+ * (stale-list quirk B13 included), which is the list the reference's
+ * ErrorMetricsResult::fill (adjust_results.h:392-463) walks at the end of
+ * solveFrames (logResultsErrorMetrics, adjust_base.cpp:1118,1201) and
+ * create_deviation_attrs_on_node (adjust_results_helpers.cpp:213-246) turns
+ * into averageDeviation / maximumDeviation / maximumDeviationFrame.  A caller
+ * that solves with NULL list pointers gets what the results UI shows from
+ * (num_frames + num_markers) entries instead of the per-residual lists.
+ *
+ * Purely additive (MMBA_ABI_VERSION stays 12): a new struct and new entry
+ * points; no existing struct or function changes.
+ *
+ * Observation i counts at frame obs_frame[i] and marker obs_marker[i]
+ * (errorToMarkerList's keys; on a B4-remapped plan that is marker i, not the
+ * flat marker whose geometry it borrows).  count counts every observation;
+ * avg is the plain IEEE sum / count (a NaN propagates; 0 without
+ * observations); max starts at 0 and is taken with >, so a NaN never wins;
+ * the arg-max is -1 when nothing exceeded 0.  Among equal maxima the lowest
+ * observation index wins (the reference iterates an unordered map).  A
+ * segment's sum depends only on its values in ascending observation order
+ * and on their number -- not on the device's observation order, the plan's
+ * solver path or the shard count: a frame's numbers are the same bits on an
+ * unsharded, a sharded and a multi-device plan, and repeated calls return
+ * the same bits.  A marker whose observations straddle a shard boundary has
+ * its shards' sums added (and, among equal maxima, the lowest frame).
+ *
+ * MMBA_ERR_INVALID when the last call on the plan was neither a solve nor a
+ * measure (as mmba_plan_outputs).  Sharded plans: a collective, every rank
+ * returns whole arrays; a multi-device plan drives all its shards from the
+ * one call.  Every pointer may be NULL. */
+typedef struct mmba_error_metrics {
+    int32_t *frame_count;      /* [num_frames]  observations at the frame            */
+    double *frame_avg;         /* [num_frames]  sum of deviations / count; 0 if none */
+    double *frame_max;         /* [num_frames]  largest deviation; 0 if none         */
+    int32_t *frame_max_marker; /* [num_frames]  its marker index; -1 if none         */
+    int32_t *marker_count;     /* [num_markers]                                      */
+    double *marker_avg;        /* [num_markers] averageDeviation                     */
+    double *marker_max;        /* [num_markers] maximumDeviation                     */
+    int32_t *marker_max_frame; /* [num_markers] maximumDeviationFrame (frame index)  */
+} mmba_error_metrics;
+int mmba_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out);
+
 /* Per-frame solve mode (FrameSolveMode::kPerFrame, adjust_base.cpp:1430-1484):
  * one solveFrames per frame over that frame's observations and the
  * parameters keyed at it plus every static parameter; results[num_frames]
@@ -785,6 +829,15 @@ int mmba_debug_reduced_residual(mmba_plan *plan, const double *x, double lam, do
  * call; each writes its own entries and rows into the caller's arrays. */
 int mmba_debug_damped_step(mmba_plan *plan, const double *x, double lam, double *step_out,
                            double *g_out, double *diag_out, double *fjac_out);
+
+/* Test hook (not part of the solver seam): mmba_plan_error_metrics' segment
+ * lists, built by the same host code from the given observation keys, and its
+ * kernel, run on the caller's err_dist [num_obs] -- shapes and values no
+ * small scene produces.  MMBA_ERR_INVALID for a key out of range. */
+int mmba_debug_error_metrics(mmba_context *ctx, int32_t num_frames, int32_t num_markers,
+                             int32_t num_obs, const int32_t *obs_marker,
+                             const int32_t *obs_frame, const double *err_dist,
+                             mmba_error_metrics *out);
 
 #ifdef __cplusplus
 }

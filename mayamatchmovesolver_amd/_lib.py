@@ -99,6 +99,12 @@ def lib():
                                       C.POINTER(abi.MmbaCallbacks), C.POINTER(abi.MmbaTrace)]
         L.mmba_plan_outputs.restype = C.c_int
         L.mmba_plan_outputs.argtypes = [C.c_void_p, dp, dp, dp]
+        L.mmba_plan_error_metrics.restype = C.c_int
+        L.mmba_plan_error_metrics.argtypes = [C.c_void_p, C.POINTER(abi.MmbaErrorMetrics)]
+        L.mmba_debug_error_metrics.restype = C.c_int
+        L.mmba_debug_error_metrics.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp,
+                                               C.POINTER(abi.MmbaErrorMetrics)]
         L.mmba_solve.restype = C.c_int
         L.mmba_solve.argtypes = [C.c_void_p, C.POINTER(abi.MmbaProblem),
                                  C.POINTER(abi.MmbaOptions), dp, dp, dp, dp,

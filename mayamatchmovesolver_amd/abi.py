@@ -248,6 +248,21 @@ class MmbaKernelStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class MmbaErrorMetrics(C.Structure):
+    """mmba_error_metrics: per-frame and per-marker deviation metrics (every
+    pointer may be NULL)."""
+    _fields_ = [
+        ("frame_count", _i32p),
+        ("frame_avg", _f64p),
+        ("frame_max", _f64p),
+        ("frame_max_marker", _i32p),
+        ("marker_count", _i32p),
+        ("marker_avg", _f64p),
+        ("marker_max", _f64p),
+        ("marker_max_frame", _i32p),
+    ]
+
+
 # Functions exported by libmmba.so (checked by tests/test_abi.py against
 # include/mmba.h).
 EXPORTED_SYMBOLS = [
@@ -284,10 +299,12 @@ EXPORTED_SYMBOLS = [
     "mmba_plan_jacobian",
     "mmba_plan_solve",
     "mmba_plan_outputs",
+    "mmba_plan_error_metrics",
     "mmba_solve",
     "mmba_plan_kernel_stats",
     "mmba_debug_set_path",
     "mmba_debug_band_solve",
     "mmba_debug_comm_allreduce",
     "mmba_debug_dgemm",
+    "mmba_debug_error_metrics",
 ]

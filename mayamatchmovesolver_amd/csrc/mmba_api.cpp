@@ -372,6 +372,21 @@ int mmba_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,
     })
 }
 
+int mmba_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out) {
+    if (!plan || !out) return MMBA_ERR_INVALID;
+    if (plan->group) return group_plan_error_metrics(plan, out);
+    if (!plan->impl.outputs_ready) {
+        set_error("invalid: error metrics without a solve or measure before them");
+        return MMBA_ERR_INVALID;
+    }
+    MMBA_GUARD({
+        Plan &p = plan->impl;
+        MMBA_HIP(hipSetDevice(p.ctx->device));
+        p.error_metrics(out);
+        return MMBA_OK;
+    })
+}
+
 int mmba_plan_set_attr_values(mmba_plan *plan, const double *attr_values) {
     if (!plan || !attr_values) return MMBA_ERR_INVALID;
     if (plan->group) return group_plan_set_attr_values(plan, attr_values);
@@ -667,5 +682,31 @@ int mmba_debug_band_solve(mmba_context *ctx, int nb, int w, int nG, int P, const
     return MMBA_OK;
 }
 
+int mmba_debug_error_metrics(mmba_context *ctx, int32_t num_frames, int32_t num_markers,
+                             int32_t num_obs, const int32_t *obs_marker,
+                             const int32_t *obs_frame, const double *err_dist,
+                             mmba_error_metrics *out) {
+    if (!ctx || !out || num_frames < 0 || num_markers < 0 || num_obs < 0 ||
+        (num_obs > 0 && (!obs_marker || !obs_frame || !err_dist)))
+        return MMBA_ERR_INVALID;
+    for (int i = 0; i < num_obs; ++i)
+        if (obs_marker[i] < 0 || obs_marker[i] >= num_markers || obs_frame[i] < 0 ||
+            obs_frame[i] >= num_frames) {
+            set_error("invalid: observation key out of range");
+            return MMBA_ERR_INVALID;
+        }
+    MMBA_GUARD({
+        MMBA_HIP(hipSetDevice(ctx->device));
+        Plan p;
+        p.ctx = ctx;
+        p.s = ctx->stream;
+        std::vector<int> dev_of_own(num_obs);
+        for (int i = 0; i < num_obs; ++i) dev_of_own[i] = i;
+        p.setup_metrics(num_frames, num_markers, num_obs, obs_marker, obs_frame, dev_of_own);
+        p.d_ed = p.upload(err_dist, (size_t)num_obs);
+        p.error_metrics(out);
+    });
+    return MMBA_OK;
+}
 
 }  // extern "C"

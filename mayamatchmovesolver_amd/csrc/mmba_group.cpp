@@ -576,6 +576,21 @@ int group_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,
     return g.run(f);
 }
 
+// every shard joins the collectives; shard 0 writes the caller's arrays
+int group_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out) {
+    ShardGroup &g = *plan->group;
+    for (int k = 0; k < g.n; ++k)  // (checked here: a shard failing alone ends the group)
+        if (!g.plans[k]->impl.outputs_ready) {
+            set_error("invalid: error metrics without a solve or measure before them");
+            return MMBA_ERR_INVALID;
+        }
+    mmba_error_metrics none{};
+    const std::function<int(int)> f = [&](int k) -> int {
+        return mmba_plan_error_metrics(g.plans[k], k == 0 ? out : &none);
+    };
+    return g.run(f);
+}
+
 int group_plan_set_attr_values(mmba_plan *plan, const double *attr_values) {
     ShardGroup &g = *plan->group;
     const std::function<int(int)> f = [&](int k) -> int {

@@ -449,4 +449,27 @@ void launch_ne_rs(hipStream_t s, const DevProblem &P, const double *J, const int
                   const int *nloc, const double *f, double *Acc, double *Acg, double *g);
 void launch_rs_offdiag(hipStream_t s, const DevProblem &P, const SView &V);
 
+// Per-frame and per-marker deviation metrics (mmba_metrics.hip): segments
+// [0, F) are the frames, [F, F + K) the markers.  Segment g holds the entries
+// [seg_off[g], seg_off[g + 1]) of idx (index into errorDistanceList as the
+// device holds it) and key (the entry's marker index on a frame segment, its
+// frame index on a marker segment), in ascending reference order.  seg_list
+// names the segments by lane-group width: n4 of 4 lanes, then n16 of 16, then
+// n64 of a whole wave (metrics_width).
+struct MetricsDev {
+    int S, n4, n16, n64;
+    const int *seg_off, *idx, *key, *seg_list;
+    // [sum (S) | max (S)] and [count (S) | key of the max, -1 when none (S)]
+    double *res_d;
+    int *res_i;
+};
+// lanes that reduce a segment of n entries: a function of n alone
+inline int metrics_width(int n) { return n <= 16 ? 4 : n <= 128 ? 16 : 64; }
+void launch_error_metrics(hipStream_t s, const MetricsDev &T, const double *ed);
+// sharded plans: the shards' results merged through coll [sum | count | max |
+// arg key] (4 S doubles) between the plan's all-reduces
+void launch_metrics_pack(hipStream_t s, const MetricsDev &T, double *coll);
+void launch_metrics_argkey(hipStream_t s, const MetricsDev &T, double *coll);
+void launch_metrics_unpack(hipStream_t s, const MetricsDev &T, const double *coll);
+
 }  // namespace mmba

@@ -133,6 +133,7 @@ Plan::~Plan() {
     if (h_xstage) (void)hipHostFree(h_xstage);
     if (h_seq) (void)hipHostFree(h_seq);
     if (h_pack) (void)hipHostFree(h_pack);
+    if (h_met) (void)hipHostFree(h_met);
 }
 
 static void require(bool c, const char *what) {
@@ -1551,6 +1552,12 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     d_var_cf = upload(var_cf);
     d_stale = upload(stale);
     d_ref_of_dev = upload(ref_of_dev);
+    {  // deviation metrics: this shard's own observations, keyed as the caller keys them
+        std::vector<int> dev_of_own(Mg, -1);
+        for (int i = 0; i < M; ++i)
+            if (obs_own_g[ref_of_dev[i]]) dev_of_own[ref_of_dev[i]] = i;
+        setup_metrics(F, nK, Mg, pr->obs_marker, pr->obs_frame, dev_of_own);
+    }
     if (nranks == 1 && M > 0) {  // the host-mapped hand-back gathers in reference order
         std::vector<int> dev_of_ref(M, 0);
         for (int i = 0; i < M; ++i) dev_of_ref[ref_of_dev[i]] = i;

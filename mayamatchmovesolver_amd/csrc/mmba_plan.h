@@ -630,6 +630,22 @@ struct Plan {
     long long ne_split_launches = 0;  // k_ne_cf_split launches (launch_ne took the split branch)
     long long trial_red_folds = 0;    // trials reduced and decided inside k_jac_ne_u (TrialRed)
     double *pre_hb_map[3] = {nullptr, nullptr, nullptr};
+    // per-frame / per-marker deviation metrics (mmba_plan_error_metrics,
+    // mmba_metrics.hip): the segment lists of this shard's own observations,
+    // built once from the global problem, the device result block and its
+    // page-locked mirror (one launch, one copy, one wait per call); sharded:
+    // the scratch the shards' results are merged through
+    MetricsDev met{};
+    int met_F = 0, met_K = 0;
+    double *d_met_coll = nullptr;
+    char *h_met = nullptr;  // pinned: [sum | max] doubles, then [count | arg] ints
+    // dev_of_own[r]: index into d_ed of global observation r, -1 when another
+    // shard owns it
+    void setup_metrics(int F, int K, int Mg, const int32_t *obs_marker, const int32_t *obs_frame,
+                       const std::vector<int> &dev_of_own);
+    // one launch, one copy, one wait (sharded: the merge between them); NULL
+    // members of out are skipped (a group plan's shards other than 0 pass none)
+    void error_metrics(mmba_error_metrics *out);
 };
 
 }  // namespace mmba
@@ -659,6 +675,7 @@ int group_debug_damped_step(mmba_plan *plan, const double *x, double lam, double
                             double *g_out, double *diag_out, double *fjac_out);
 int group_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,
                        double *err_dist_out);
+int group_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out);
 int group_plan_set_attr_values(mmba_plan *plan, const double *attr_values);
 int group_plan_solve_per_frame(mmba_plan *plan, double *x_inout, mmba_result *results,
                                const mmba_callbacks *cb);

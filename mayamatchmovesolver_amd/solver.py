@@ -46,6 +46,8 @@ class SolveResult:
 
     problem: Optional[Problem] = None
     x0: Optional[np.ndarray] = None
+    # ``Solver.solve(metrics=True)``: the dict of ``Solver.error_metrics()``
+    metrics: Optional[Dict] = None
 
     @property
     def accepted_x(self):
@@ -74,6 +76,64 @@ class SolveResult:
             "iteration_jacobian_num=%d" % int(r["jacobian_evals"]),
             "user_interrupted=%d" % int(r["user_interrupted"]),
         ]
+
+    def error_metric_strings(self, frame_numbers=None, marker_names=None) -> List[str]:
+        """The result lines of ``ErrorMetricsResult::appendToMStringArray``
+        (adjust_results.h:519-558) that ``mmSolver.api.SolveResult`` parses
+        (solveresult.py:201-244), from ``metrics`` (``solve(metrics=True)``):
+        ``error_per_frame=<frame>#<avg>`` for every frame with observations
+        (``fill`` makes no entry for the others) and, when ``err_dist`` was
+        fetched, ``error_per_marker_per_frame=<marker>#<frame>#<deviation>``
+        first, as the reference orders them.  ``frame_numbers`` /
+        ``marker_names``: the scene's frame values and marker node names per
+        index (default: the indices, ``marker_<i>``)."""
+        if self.metrics is None:
+            raise ValueError("no metrics: solve(metrics=True)")
+        mt, p = self.metrics, self.problem
+        nf = len(mt["frame_count"])
+        frames = np.arange(nf) if frame_numbers is None else frame_numbers
+        out = []
+        if self.err_dist is not None and p is not None:
+            nk = len(mt["marker_count"])
+            names = (["marker_%d" % k for k in range(nk)] if marker_names is None
+                     else marker_names)
+            for i in range(p.num_obs):
+                out.append("error_per_marker_per_frame=%s%s%s%s%s" % (
+                    names[int(p.obs_marker[i])], RESULT_SPLIT_CHAR,
+                    _num(frames[int(p.obs_frame[i])]), RESULT_SPLIT_CHAR,
+                    _num(self.err_dist[i])))
+        for f in range(nf):
+            if mt["frame_count"][f] > 0:
+                out.append("error_per_frame=%s%s%s" % (_num(frames[f]), RESULT_SPLIT_CHAR,
+                                                      _num(mt["frame_avg"][f])))
+        return out
+
+
+RESULT_SPLIT_CHAR = "#"  # CMD_RESULT_SPLIT_CHAR (adjust_defines.h:62)
+
+
+def deviation_summary(frames, values):
+    """(averageDeviation, maximumDeviation, maximumDeviationFrame) of one
+    deviation series as ``create_deviation_attrs_on_node``
+    (adjust_results_helpers.cpp:213-268) sets them on the solve node from the
+    per-frame series (and on a marker from its own): a sequential average, the
+    maximum from 0 with ``>`` and its frame, -1 when nothing exceeded 0."""
+    count, total, vmax, fmax = 0, 0.0, -0.0, -1.0
+    for f, v in zip(frames, values):
+        total += float(v)
+        count += 1
+        if v > vmax:
+            vmax, fmax = float(v), float(f)
+    return (total / count if count > 0 else total), vmax, int(fmax)
+
+
+def solve_node_summary(metrics, frame_numbers=None):
+    """``deviation_summary`` of the per-frame series of an
+    ``error_metrics()`` dict (the frames that have observations)."""
+    cnt = np.asarray(metrics["frame_count"])
+    frames = np.arange(cnt.size) if frame_numbers is None else np.asarray(frame_numbers)
+    has = cnt > 0
+    return deviation_summary(frames[has], np.asarray(metrics["frame_avg"])[has])
 
 
 class Context:
@@ -327,7 +387,7 @@ class Solver:
         return fjac.reshape(n, m).T
 
     def solve(self, x0=None, trace_capacity=4096, interrupt=None, out=None,
-              fetch=True) -> SolveResult:
+              fetch=True, metrics=False) -> SolveResult:
         """LM solve from x0 (internal parameters).  ``SolveResult.x`` is the
         solved x as lmder leaves paramList; ``result["error_is_better"]`` says
         whether solveFrames would write it back (``accepted_x``).
@@ -337,7 +397,10 @@ class Solver:
         fresh ones (a caller solving repeatedly keeps its buffers).
         ``fetch=False``: the per-residual outputs stay in HBM (NULL output
         pointers; ``fvec`` / ``err_user`` / ``err_dist`` are None) until
-        ``outputs()`` fetches them."""
+        ``outputs()`` fetches them.
+        ``metrics=True``: ``SolveResult.metrics`` carries ``error_metrics()``
+        of this solve (with ``fetch=False`` too: a few values per frame and per
+        marker instead of the per-residual lists)."""
         p = self.problem
         m, M = p.num_residuals, p.num_obs
         x = np.array(p.x0 if x0 is None else x0, dtype=np.float64)
@@ -366,7 +429,8 @@ class Solver:
             check(rc)
         return SolveResult(x=x, fvec=fvec, err_user=eu, err_dist=ed, result=res.as_dict(),
                            fnorm_trace=tbuf[:min(tr.count, trace_capacity)].copy(), problem=p,
-                           x0=np.array(p.x0 if x0 is None else x0, dtype=np.float64))
+                           x0=np.array(p.x0 if x0 is None else x0, dtype=np.float64),
+                           metrics=self.error_metrics() if metrics else None)
 
 
     def outputs(self, out=None):
@@ -378,6 +442,32 @@ class Solver:
         fvec, eu, ed = out if out is not None else (np.zeros(m), np.zeros(m), np.zeros(M))
         check(lib().mmba_plan_outputs(self._h, _dp(fvec), _dp(eu), _dp(ed)))
         return fvec, eu, ed
+
+    def error_metrics(self, members=None) -> Dict:
+        """Per-frame and per-marker deviation metrics of the last ``solve`` /
+        ``measure`` (``mmba_plan_error_metrics``), reduced on the device from
+        the errorDistanceList kept in HBM: a dict of numpy arrays named as the
+        members of ``mmba_error_metrics`` (``members``: only those; the others
+        are passed as NULL)."""
+        p = self.problem
+        F, K = p.num_frames, p.num_markers
+        # the whole set's arrays and descriptor are kept across calls (the
+        # ctypes pointers cost more than the call on a small scene); the
+        # caller gets copies
+        keep = getattr(self, "_met", None) if members is None else None
+        if keep is None:
+            mt = {name: np.zeros(max(F if name.startswith("frame") else K, 1),
+                                 dtype=np.int32 if typ is abi._i32p else np.float64)
+                  for name, typ in abi.MmbaErrorMetrics._fields_
+                  if members is None or name in members}
+            st = abi.MmbaErrorMetrics(*[mt[name].ctypes.data_as(typ) if name in mt else None
+                                        for name, typ in abi.MmbaErrorMetrics._fields_])
+            keep = (mt, st)
+            if members is None:
+                self._met = keep
+        mt, st = keep
+        check(lib().mmba_plan_error_metrics(self._h, C.byref(st)))
+        return {name: a[:F if name.startswith("frame") else K].copy() for name, a in mt.items()}
 
     def set_attr_values(self, attr_values):
         """Replace the scene's attribute values of this plan
@@ -478,3 +568,25 @@ def debug_band_solve(ctx: "Context", S: np.ndarray, nb: int, w: int, nG: int, pa
                                           _dp(S), _dp(r), _dp(x), C.byref(yn), C.byref(pu)))
         return x, yn.value, pu.value
     return solve
+
+
+def debug_error_metrics(ctx: "Context", num_frames: int, num_markers: int, obs_marker, obs_frame,
+                        err_dist, members=None) -> Dict:
+    """Test hook (``mmba_debug_error_metrics``): ``Solver.error_metrics()``'s
+    segment lists and kernel on a caller-given key list and errorDistanceList.
+    ``members``: the names to fill (the others are passed as NULL)."""
+    mk = np.ascontiguousarray(obs_marker, dtype=np.int32)
+    fr = np.ascontiguousarray(obs_frame, dtype=np.int32)
+    ed = np.ascontiguousarray(err_dist, dtype=np.float64)
+    assert mk.size == fr.size == ed.size
+    F, K = int(num_frames), int(num_markers)
+    mt = {name: np.zeros(max(F if name.startswith("frame") else K, 1),
+                         dtype=np.int32 if typ is abi._i32p else np.float64)
+          for name, typ in abi.MmbaErrorMetrics._fields_
+          if members is None or name in members}
+    st = abi.MmbaErrorMetrics(*[mt[name].ctypes.data_as(typ) if name in mt else None
+                                for name, typ in abi.MmbaErrorMetrics._fields_])
+    check(lib().mmba_debug_error_metrics(ctx.handle, F, K, int(ed.size),
+                                         mk.ctypes.data_as(abi._i32p),
+                                         fr.ctypes.data_as(abi._i32p), _dp(ed), C.byref(st)))
+    return {name: a[:F if name.startswith("frame") else K] for name, a in mt.items()}
