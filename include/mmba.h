@@ -719,7 +719,9 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                                       solved bundle, its parameter pass) */
 #define MMBA_PATH_LENS_CF 11       /* 0: every lens coefficient a global parameter (an
                                       animated one read by one camera-frame's rows joins
-                                      that camera-frame's block otherwise) */
+                                      that camera-frame's block otherwise; one read by
+                                      several cameras' rows: MMBA_PATH_LENS_SHARED).  More
+                                      than 48 global parameters are refused */
 #define MMBA_PATH_DEST_LANE 12     /* 0 / 1: small off-diagonal Schur destinations never /
                                       always by a lane each (default: where they are most
                                       of at least 16,384) */
@@ -774,7 +776,15 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                                        the two is skipped (same bits); the factorisation flag
                                        is then converted by the trial's back substitution.
                                        Default: 1 */
-#define MMBA_PATH_NUM 26
+#define MMBA_PATH_LENS_SHARED 26  /* an animated lens coefficient read by several cameras'
+                                     rows at its frame: 1 it joins the block of the frame's
+                                     lowest-numbered reading camera-frame and the other
+                                     readers couple to it through off-diagonal camera-frame
+                                     blocks (wherever the plan is eligible: the conditions of
+                                     MMBA_PATH_LENS_CF, one device, no solved bundle), 0 it is
+                                     always a global parameter; default: the shared form only
+                                     where the global form would exceed 48 global parameters */
+#define MMBA_PATH_NUM 27
 int mmba_debug_set_path(int key, int value);
 
 /* Test hook (not part of the solver seam): solve S x = r with the device

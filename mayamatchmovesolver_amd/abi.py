@@ -50,7 +50,8 @@ PATH_PRE_HANDBACK = 22
 PATH_PRE_SCHUR = 23
 PATH_BACKSUB_GROUP = 24
 PATH_TRIAL_RED_FOLD = 25
-PATH_NUM = 26
+PATH_LENS_SHARED = 26
+PATH_NUM = 27
 
 FILM_FIT_FILL = 0
 FILM_FIT_HORIZONTAL = 1

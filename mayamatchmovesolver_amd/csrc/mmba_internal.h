@@ -390,6 +390,18 @@ struct DevProblem {
     // (column, global index) pairs, NGMAX slots each
     const int *cf_rs_gcnt, *cf_rs_gcol, *cf_rs_gidx;
     double *rs_Aoff;
+    // animated lens coefficients shared by several cameras (Plan::build,
+    // mmba_lens_shared.hip): ls_ng host camera-frames, each with the
+    // coefficients its block hosts and the foreign camera-frames of its frame
+    // whose rows read them (ls_nl links in all).  ls_tab, one table:
+    //   host[ng] | nh[ng] | link_off[ng + 1] | hpar[ng PCMAX] | hpos[ng PCMAX]
+    //   | link_cf[nl] | link_grp[nl]
+    // (hpar: parameter id, hpos: its row in the host block).  ls_Aoff[(k PCMAX
+    // + a) PCMAX + h]: the coupling block A(foreign camera-frame of link k,
+    // hosted coefficient h).  ls_ng == 0 on every other plan.
+    int ls_ng, ls_nl;
+    const int *ls_tab;
+    double *ls_Aoff;
 };
 
 __device__ __forceinline__ size_t widx(const DevProblem &P, int k, int i) {

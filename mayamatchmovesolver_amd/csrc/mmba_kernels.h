@@ -448,6 +448,11 @@ void launch_jacobian_rs(hipStream_t s, const DevProblem &P, const double *ext_pe
 void launch_ne_rs(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
                   const int *nloc, const double *f, double *Acc, double *Acg, double *g);
 void launch_rs_offdiag(hipStream_t s, const DevProblem &P, const SView &V);
+// shared animated lens coefficients (mmba_lens_shared.hip): the foreign rows'
+// terms of the normal equations, and their coupling blocks into S
+void launch_ne_lens_shared(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
+                           const int *nloc, const double *f, double *Acc, double *Acg, double *g);
+void launch_lens_shared_offdiag(hipStream_t s, const DevProblem &P, const SView &V);
 
 // Per-frame and per-marker deviation metrics (mmba_metrics.hip): segments
 // [0, F) are the frames, [F, F + K) the markers.  Segment g holds the entries

@@ -870,7 +870,10 @@ __global__ void __launch_bounds__(128, CEN ? 1 : 2) k_jacobian(DevProblem P, con
             // (adjust_solveFunc.cpp frameIndexEnable): the observations of
             // other frames that read the instance it writes keep f - f = 0
             if (P.p_frame[p] >= 0 && P.p_frame[p] != fr) continue;
-            if (P.p_class[p] == PC_CF) continue;  // a camera-frame block column (VF_LENS)
+            // a camera-frame block column (VF_LENS) of this row's own block;
+            // another camera-frame's block hosts a coefficient several cameras
+            // read (mmba_lens_shared.hip): a foreign row emits its column here
+            if (P.p_class[p] == PC_CF && P.p_blk[p] == cf) continue;
             double lc[MMBA_LENS_NUM_ATTRS];
             inst_coeffs(P, inst, Override{P.p_attr[p], ext_pert[p]}, lc);
             emit_s(p, residual_l<LT>(P, rec0, bp0, mx, my, sw, hl, lc), step[p], [&]() {
@@ -4350,7 +4353,7 @@ void launch_jacobian(hipStream_t s, const DevProblem &P, const double *recs,
 // observation over the whole GPU.
 bool jac_ne_fusable(const DevProblem &P, int ncv) {
     return P.nG == 0 && P.pc_uniform == ncv && (ncv == 6 || ncv == 7) &&
-           P.nrows == 0 && !P.loss_on && P.ncf >= 256 && !P.rs;
+           P.nrows == 0 && !P.loss_on && P.ncf >= 256 && !P.rs && !P.ls_ng;
 }
 void launch_jac_ne(hipStream_t s, const DevProblem &P, const double *recs, const double *step,
                    int solver_type, double *J, int *jcol, int *nloc, const int *stale_param,
@@ -4717,8 +4720,10 @@ void launch_b15_jp(hipStream_t s, int n, const double *xs, const double *u, cons
     k_b15_jp<<<1, 1024, 0, s>>>(n, xs, u, c, sp, out);
 }
 bool ne_epilogue_fusable(const DevProblem &P) {
+    // (shared lens coefficients: the foreign rows' terms of a host block's
+    // diagonal come after the camera-frame pass, launch_ne_lens_shared)
     return P.nG == 0 && (P.JB || P.nbs == 0) && (P.pc_uniform == 6 || P.pc_uniform == 7) &&
-           !P.rs;
+           !P.rs && !P.ls_ng;
 }
 bool launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
                const int *nloc, const double *f, double *Acc, double *Acg, double *Abb,
@@ -4770,6 +4775,9 @@ bool launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *j
         }
 #undef MMBA_NE_U
     }
+    // shared lens coefficients: what the other cameras' rows add to their
+    // host blocks, and the coupling blocks
+    if (P.ls_ng > 0) launch_ne_lens_shared(s, P, J, jcol, nloc, f, Acc, Acg, g);
     if (P.nbs > 0) {
         if (P.JB)  // every solved bundle fast and no global parameters
             k_ne_bnd_jb<<<nblk(P.nB, NE_BND_TPB), NE_BND_TPB, 0, s>>>(P, Abb, g, E);
@@ -4835,6 +4843,7 @@ void launch_schur_init(hipStream_t s, const DevProblem &P, const double *Acc, co
     else
         k_schur_init<<<nblk(n, 256), 256, 0, s>>>(P, Acc, Acg, Agg, g, diag, lam, V, npad, rhs);
     if (P.rs) launch_rs_offdiag(s, P, V);  // camera-frame coupling blocks
+    if (P.ls_ng > 0) launch_lens_shared_offdiag(s, P, V);
 }
 void launch_schur_pairs(hipStream_t s, const DevProblem &P, const double *W, const double *Wg,
                         const double *tb, const SView &V, double *rhs) {

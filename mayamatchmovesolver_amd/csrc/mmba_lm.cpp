@@ -770,9 +770,11 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
         // zeroed once at plan build; the partitioned path factors in place
         if (band && bs.red) {  // d_rhs is the tail of the block, zeroed above
             MMBA_HIP(hipMemsetAsync(bs.red, 0, sizeof(double) * (bs.red_count - nRpad), s));
-        } else if (band && ((!bs.use_bcr && kind != Reduced::BlockDiag) || rs_bnd)) {
+        } else if (band && ((!bs.use_bcr && kind != Reduced::BlockDiag) || rs_bnd || lens_shared)) {
             // (rolling shutter with solved bundles: k_rs_offdiag writes the
-            // coupling blocks, so k_schur_dest subtracts instead of assigning)
+            // coupling blocks, so k_schur_dest subtracts instead of assigning;
+            // shared lens coefficients: their coupling blocks lie outside the
+            // entries the diagonal blocks rewrite)
             const int nb = nR - nG;
             MMBA_HIP(hipMemsetAsync(bs.Bd, 0, sizeof(double) * (size_t)nb * (bw + 1), s));
             if (nG > 0) MMBA_HIP(hipMemsetAsync(bs.Ga, 0, sizeof(double) * (size_t)nG * nb, s));

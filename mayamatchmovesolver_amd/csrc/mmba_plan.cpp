@@ -551,6 +551,7 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     // instead of the global arrow (VERDICT r4 "next" 7: focus breathing over
     // more than NGMAX frames).  Forward differences, no rolling shutter ----
     std::vector<int> lens_cam(n, -2);  // -2: no reader, -1: several cameras
+    std::vector<std::set<int>> lens_readers(n);  // the cameras whose rows read it at its frame
     if (!rs_on && !central && path_choice(MMBA_PATH_LENS_CF) != 0 && !inst_lens_h.empty()) {
         require(M == Mg, "lens classification before sharding");
         for (int r = 0; r < Mg; ++r) {
@@ -561,35 +562,96 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
                 if (pr->param_frame[p] != pr->obs_frame[r]) continue;
                 int &c = lens_cam[p];
                 c = c == -2 ? obs_cam[r] : (c == obs_cam[r] ? c : -1);
+                lens_readers[p].insert(obs_cam[r]);
             }
         }
     }
+    // ---- ... and one whose column reaches the rows of SEVERAL cameras at
+    // its frame (two cameras on one lens, C5 with focus breathing): the shared
+    // form puts it into the block of the frame's lowest-numbered reading
+    // camera-frame, its host; the other readers are foreign -- their rows
+    // carry its column beside their own block's (k_jacobian's lens loop) and
+    // couple their camera-frame to the host's through an off-diagonal block
+    // (mmba_lens_shared.hip).  A coefficient no row reads at its frame (a zero
+    // column) is then hosted by the frame's first camera-frame.  Taken where
+    // the global form would exceed NGMAX (MMBA_PATH_LENS_SHARED = 1: wherever
+    // eligible, 0: never); needs what the one-camera form needs, one device
+    // and no solved bundle (a foreign row's W row would span two blocks) ----
+    bool has_anim_lens = false, has_solved_bundle = false;
+    for (int p = 0; p < n; ++p) {
+        const int a = pr->param_attr[p];
+        if (!attr_lcams[a].empty() && pr->param_frame[p] >= 0) has_anim_lens = true;
+        if (attr_lcams[a].empty() && attr_cams[a].empty() && attr_bnds[a].size() == 1 &&
+            pr->param_frame[p] < 0)
+            has_solved_bundle = true;
+    }
+    const int shared_pin = path_choice(MMBA_PATH_LENS_SHARED);
+    const char *shared_off = nullptr;  // the condition that keeps the shared form off
+    if (path_choice(MMBA_PATH_LENS_CF) == 0) shared_off = "MMBA_PATH_LENS_CF = 0";
+    else if (shared_pin == 0) shared_off = "MMBA_PATH_LENS_SHARED = 0";
+    else if (rs_on) shared_off = "rolling shutter";
+    else if (central) shared_off = "central differences";
+    else if (nranks > 1) shared_off = "sharded plan";
+    else if (has_solved_bundle) shared_off = "solved bundles";
+    // the host camera of a shared coefficient, -1: it stays global
+    auto shared_host = [&](int p) -> int {
+        if (lens_cam[p] == -1) return *lens_readers[p].begin();
+        auto it = cf_id.lower_bound({pr->param_frame[p], INT32_MIN});  // lens_cam -2: no reader
+        return (it != cf_id.end() && it->first.first == pr->param_frame[p]) ? it->first.second : -1;
+    };
     // ---- classify parameters ----
     std::vector<int> p_class(n), p_blk(n, -1), p_pos(n, -1), p_both(n, 0), p_lens(n, 0);
+    std::vector<int> p_shared(n, 0);  // hosted in the shared form
     std::vector<std::pair<int, int>> p_cfkey(n, {-1, -1});
-    for (int p = 0; p < n; ++p) {
-        const int a = pr->param_attr[p], fp = pr->param_frame[p];
-        const auto &cams = attr_cams[a];
-        const auto &bnds = attr_bnds[a];
-        const auto &lc = attr_lcams[a];
-        if (!lc.empty() && (!cams.empty() || !bnds.empty()))
-            throw Unsupported{"attribute used both as lens coefficient and geometry"};
-        p_both[p] = (!cams.empty() && !bnds.empty()) ? 1 : 0;
-        if (lc.empty() && bnds.empty() && cams.size() == 1 && fp >= 0) {
-            p_class[p] = PC_CF;
-            p_cfkey[p] = {fp, cams[0]};
-            cf_id[{fp, cams[0]}] = 0;
-        } else if (lc.empty() && cams.empty() && bnds.size() == 1 && fp < 0) {
-            p_class[p] = PC_B;
-            p_blk[p] = bnds[0];
-        } else if (!lc.empty() && fp >= 0 && lens_cam[p] >= 0) {
-            p_class[p] = PC_CF;
-            p_lens[p] = 1;
-            p_cfkey[p] = {fp, lens_cam[p]};
-        } else {
-            p_class[p] = PC_G;
+    lens_shared = false;
+    // shared: the several-camera form too; returns the number of globals
+    auto classify = [&](bool shared) -> int {
+        int ng = 0;
+        for (int p = 0; p < n; ++p) {
+            const int a = pr->param_attr[p], fp = pr->param_frame[p];
+            const auto &cams = attr_cams[a];
+            const auto &bnds = attr_bnds[a];
+            const auto &lc = attr_lcams[a];
+            if (!lc.empty() && (!cams.empty() || !bnds.empty()))
+                throw Unsupported{"attribute used both as lens coefficient and geometry"};
+            p_both[p] = (!cams.empty() && !bnds.empty()) ? 1 : 0;
+            if (lc.empty() && bnds.empty() && cams.size() == 1 && fp >= 0) {
+                p_class[p] = PC_CF;
+                p_cfkey[p] = {fp, cams[0]};
+                cf_id[{fp, cams[0]}] = 0;
+            } else if (lc.empty() && cams.empty() && bnds.size() == 1 && fp < 0) {
+                p_class[p] = PC_B;
+                p_blk[p] = bnds[0];
+            } else if (!lc.empty() && fp >= 0 && lens_cam[p] >= 0) {
+                p_class[p] = PC_CF;
+                p_lens[p] = 1;
+                p_cfkey[p] = {fp, lens_cam[p]};
+            } else if (shared && !lc.empty() && fp >= 0 && shared_host(p) >= 0) {
+                p_class[p] = PC_CF;
+                p_lens[p] = 1;
+                p_shared[p] = 1;
+                p_cfkey[p] = {fp, shared_host(p)};
+                if (lens_cam[p] == -1) lens_shared = true;
+            } else {
+                p_class[p] = PC_G;
+                ++ng;
+            }
         }
-    }
+        return ng;
+    };
+    // the forms taken so far first; the shared form where they leave more
+    // than NGMAX globals, or where it is pinned on
+    const int ng_plain = classify(false);
+    if (!shared_off && has_anim_lens && !inst_lens_h.empty() &&
+        (shared_pin == 1 || ng_plain > NGMAX))
+        classify(true);
+    if (!lens_shared)  // no coefficient with several readers: nothing changes
+        for (int p = 0; p < n; ++p)
+            if (p_shared[p]) {
+                p_class[p] = PC_G;
+                p_lens[p] = p_shared[p] = 0;
+                p_cfkey[p] = {-1, -1};
+            }
     // number the camera-frames: frame-major (the keys' order), so a bundle
     // tracked over a window of frames couples a contiguous band; with a
     // rolling shutter and no solved bundle, camera-major instead: the
@@ -640,7 +702,12 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         if (p_class[p] == PC_G) g_param.push_back(p);
     nG = (int)g_param.size();
     if (nG > NGMAX)
-        throw Unsupported{"more than " + std::to_string(NGMAX) + " global parameters"};
+        throw Unsupported{"more than " + std::to_string(NGMAX) + " global parameters" +
+                          (has_anim_lens && shared_off
+                               ? std::string(" (animated lens coefficients shared by several "
+                                             "cameras stay global parameters: ") +
+                                     shared_off + ")"
+                               : std::string())};
     for (int q = 0; q < nG; ++q) p_pos[g_param[q]] = nCF + q;
     nR = nCF + nG;
 
@@ -744,6 +811,39 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     bw = 0;
     for (int cf = 0; cf < ncf; ++cf)
         if (cf_pc[cf] > 0) bw = std::max(bw, cf_pc[cf] - 1);
+    // shared lens coefficients: per host camera-frame the coefficients its
+    // block hosts and the foreign camera-frames whose rows read one of them
+    // (links); a link couples the foreign block with the hosted rows
+    std::vector<int> ls_host, ls_nh, ls_link_off(1, 0), ls_hpar, ls_hpos, ls_link_cf, ls_link_grp;
+    if (lens_shared)
+        for (int cf = 0; cf < ncf; ++cf) {
+            std::vector<int> hosted;
+            std::set<int> foreign;
+            for (int p : cf_params[cf]) {
+                if (!p_shared[p]) continue;
+                hosted.push_back(p);
+                for (int c : lens_readers[p])
+                    if (c != cf_cam[cf]) foreign.insert(cf_id[{cf_frame[cf], c}]);
+            }
+            if (hosted.empty() || foreign.empty()) continue;
+            const int grp = (int)ls_host.size();
+            ls_host.push_back(cf);
+            ls_nh.push_back((int)hosted.size());
+            int lo = nCF;
+            for (int h = 0; h < PCMAX; ++h) {
+                ls_hpar.push_back(h < (int)hosted.size() ? hosted[h] : -1);
+                ls_hpos.push_back(h < (int)hosted.size() ? p_pos[hosted[h]] - cf_roff[cf] : 0);
+                if (h < (int)hosted.size()) lo = std::min(lo, p_pos[hosted[h]]);
+            }
+            for (int x : foreign) {
+                // the coupling block sits below the diagonal (k_lens_shared_offdiag)
+                if (x <= cf) throw Invalid{"shared lens coefficient: host after a reader"};
+                ls_link_cf.push_back(x);
+                ls_link_grp.push_back(grp);
+                if (cf_pc[x] > 0) bw = std::max(bw, cf_roff[x] + cf_pc[x] - 1 - lo);
+            }
+            ls_link_off.push_back((int)ls_link_cf.size());
+        }
     if (rs_on)  // an observation couples its camera-frame with both neighbours
         for (int cf = 0; cf < ncf; ++cf) {
             int lo = cf_pc[cf] > 0 ? cf_roff[cf] : nCF, hi = cf_pc[cf] > 0 ? cf_roff[cf] + cf_pc[cf] - 1 : -1;
@@ -774,6 +874,9 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     }
     band = nR > 0 && bw <= WBAND_MAX;
     if (rs_on && !band) throw Unsupported{"rolling shutter: camera-frame band wider than WBAND_MAX (80)"};
+    if (lens_shared && !band)
+        throw Unsupported{"animated lens coefficients shared by several cameras: camera-frame "
+                          "band wider than WBAND_MAX (80)"};
 
     // ---- frame sharding: this shard's frames, camera-frame rows, observations
     // (own = in its frames; halo = other observations of solved bundles seen in
@@ -1514,6 +1617,19 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         D.rs_Aoff = dalloc<double>((size_t)2 * ncf * PCMAX * PCMAX);
         MMBA_HIP(hipMemsetAsync(D.rs_Aoff, 0, sizeof(double) * 2 * ncf * PCMAX * PCMAX, s));
     }
+    D.ls_ng = (int)ls_host.size();
+    D.ls_nl = (int)ls_link_cf.size();
+    D.ls_tab = nullptr;
+    D.ls_Aoff = nullptr;
+    if (D.ls_ng > 0) {
+        std::vector<int> tab;
+        for (const std::vector<int> *v :
+             {&ls_host, &ls_nh, &ls_link_off, &ls_hpar, &ls_hpos, &ls_link_cf, &ls_link_grp})
+            tab.insert(tab.end(), v->begin(), v->end());
+        D.ls_tab = upload(tab);
+        D.ls_Aoff = dalloc<double>((size_t)D.ls_nl * PCMAX * PCMAX);
+        MMBA_HIP(hipMemsetAsync(D.ls_Aoff, 0, sizeof(double) * D.ls_nl * PCMAX * PCMAX, s));
+    }
     D.loss_on = opt.robust_loss ? 1 : 0;
     D.loss_type = opt.robust_loss_type;
     D.loss_scale = opt.robust_loss_scale;
@@ -1890,7 +2006,9 @@ void Plan::setup_band(int Pforce) {
     // No solved bundle (C2, C5, per-frame solves): the camera-frame blocks are
     // uncoupled, so S is block diagonal + arrow (mmba_bdiag.hip)
     {
-        if (nB_solved == 0 && nranks == 1 && !cfblk_pc.empty() && Pforce == 0 && !rs_on) {
+        // (nor coupled by the rolling shutter or by a shared lens coefficient)
+        if (nB_solved == 0 && nranks == 1 && !cfblk_pc.empty() && Pforce == 0 && !rs_on &&
+            !lens_shared) {
             bs.use_bd = true;
             bs.P = 1;
             bs.w = w;

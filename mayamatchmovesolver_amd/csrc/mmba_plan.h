@@ -229,6 +229,9 @@ struct Plan {
     double *d_b15k = nullptr;  // [K^-1 (4), s, fail of the first solve]
     // rolling shutter (mmba.h ABI 3, mmba_rs.hip)
     bool rs_on = false;
+    // some animated lens coefficient is hosted by one camera-frame and read
+    // by others of its frame (Plan::build, mmba_lens_shared.hip)
+    bool lens_shared = false;
     double *d_ext_pertB = nullptr, *d_stepB = nullptr, *d_recsB = nullptr, *d_brecB = nullptr;
     std::vector<double> param_weight;  // paramWeightList (diag in mode 2)
     double *d_pweight = nullptr;       // ... on the device
