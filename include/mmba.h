@@ -579,6 +579,14 @@ typedef struct mmba_error_metrics {
 } mmba_error_metrics;
 int mmba_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out);
 
+/* Where the plan put each parameter: class 0 camera-frame block, 1 bundle,
+ * 2 global; block = camera-frame index (frame-major numbering) / bundle index / -1.
+ * Each array holds num_params entries (the problem's, in parameter order);
+ * either pointer may be NULL.  A group plan reports its first shard's: every
+ * shard classifies all parameters alike and numbers camera-frames and bundles
+ * over the whole problem, so the indices are the unsharded plan's. */
+int mmba_plan_param_layout(const mmba_plan *plan, int32_t *class_out, int32_t *block_out);
+
 /* Per-frame solve mode (FrameSolveMode::kPerFrame, adjust_base.cpp:1430-1484):
  * one solveFrames per frame over that frame's observations and the
  * parameters keyed at it plus every static parameter; results[num_frames]
@@ -784,7 +792,21 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                                      MMBA_PATH_LENS_CF, one device, no solved bundle), 0 it is
                                      always a global parameter; default: the shared form only
                                      where the global form would exceed 48 global parameters */
-#define MMBA_PATH_NUM 27
+#define MMBA_PATH_OBJ_CF 27       /* an object-frame parameter (an animated transform attribute
+                                     above bundles and above no camera -- a rigid object keyed
+                                     per frame) whose bundles one camera sees at its frame: 1 it
+                                     joins that camera-frame's block (wherever the plan is
+                                     eligible: forward differences, no rolling shutter, no
+                                     robust loss, one device), 0 it is always a global
+                                     parameter; default: the block form only where the global
+                                     form would exceed 48 global parameters */
+#define MMBA_PATH_OBJ_REC 28      /* 0: bundles under a moving parent transform walk the
+                                     transform chain per observation and Jacobian column; 1:
+                                     the parent's world matrix comes from object records built
+                                     once per evaluation (plans on the generic Jacobian kernel:
+                                     forward differences, no rolling shutter, one device).
+                                     Default: 1 */
+#define MMBA_PATH_NUM 29
 int mmba_debug_set_path(int key, int value);
 
 /* Test hook (not part of the solver seam): solve S x = r with the device

@@ -101,6 +101,9 @@ def lib():
         L.mmba_plan_outputs.argtypes = [C.c_void_p, dp, dp, dp]
         L.mmba_plan_error_metrics.restype = C.c_int
         L.mmba_plan_error_metrics.argtypes = [C.c_void_p, C.POINTER(abi.MmbaErrorMetrics)]
+        L.mmba_plan_param_layout.restype = C.c_int
+        L.mmba_plan_param_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]
         L.mmba_debug_error_metrics.restype = C.c_int
         L.mmba_debug_error_metrics.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), dp,

@@ -51,7 +51,9 @@ PATH_PRE_SCHUR = 23
 PATH_BACKSUB_GROUP = 24
 PATH_TRIAL_RED_FOLD = 25
 PATH_LENS_SHARED = 26
-PATH_NUM = 27
+PATH_OBJ_CF = 27
+PATH_OBJ_REC = 28
+PATH_NUM = 29
 
 FILM_FIT_FILL = 0
 FILM_FIT_HORIZONTAL = 1
@@ -301,6 +303,7 @@ EXPORTED_SYMBOLS = [
     "mmba_plan_solve",
     "mmba_plan_outputs",
     "mmba_plan_error_metrics",
+    "mmba_plan_param_layout",
     "mmba_solve",
     "mmba_plan_kernel_stats",
     "mmba_debug_set_path",

@@ -18,10 +18,10 @@ namespace mmba {
 static thread_local std::string g_last_error;
 void set_error(const std::string &msg) { g_last_error = msg; }
 
-static_assert(MMBA_PATH_NUM == 27, "one initialiser per path key");
+static_assert(MMBA_PATH_NUM == 29, "one initialiser per path key");
 static std::atomic<int> g_path[MMBA_PATH_NUM] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
                                                  -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                                                 -1, -1};
+                                                 -1, -1, -1, -1};
 int path_choice(int key) {
     return (key > 0 && key < MMBA_PATH_NUM) ? g_path[key].load() : -1;
 }
@@ -385,6 +385,16 @@ int mmba_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out) {
         p.error_metrics(out);
         return MMBA_OK;
     })
+}
+
+int mmba_plan_param_layout(const mmba_plan *plan, int32_t *class_out, int32_t *block_out) {
+    if (!plan) return MMBA_ERR_INVALID;
+    const Plan &p = plan->group ? group_first_plan(plan)->impl : plan->impl;
+    for (int j = 0; j < p.n; ++j) {
+        if (class_out) class_out[j] = p.p_class_h[j];
+        if (block_out) block_out[j] = p.p_blk_h[j];
+    }
+    return MMBA_OK;
 }
 
 int mmba_plan_set_attr_values(mmba_plan *plan, const double *attr_values) {

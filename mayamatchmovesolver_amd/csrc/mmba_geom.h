@@ -27,6 +27,17 @@ constexpr double INCH_TO_MM = 25.4;
 constexpr double MM_TO_CM = 0.1;
 constexpr int MAX_DEPTH = 16;
 
+// Workgroup b of a G-workgroup grid runs on XCD b mod 8; xcd_remap(b, G) is
+// the logical block it takes so that each XCD sweeps one contiguous range of
+// logical blocks (a bijection of [0, G)).  Kernels that walk the
+// camera-frame-sorted observations, the records they read and the Jacobian
+// they write use it alike, so a producer's lines sit in the L2 of the XCD
+// that reads them next.
+MMBA_DEV int xcd_remap(int b, int G) {
+    const int x = b & 7, idx = b >> 3, q = G >> 3, r = G & 7;
+    return x * q + min(x, r) + idx;
+}
+
 // One attribute override: the perturbed parameter of an FD column.
 struct Override {
     int attr;
@@ -198,6 +209,28 @@ MMBA_DEV void bundle_position(const DevProblem &P, int b, int f, const Override 
     }
     double W[16];
     world_matrix(P, parent, f, ov, W);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        pos[r] = W[r * 4 + 0] * tx + W[r * 4 + 1] * ty + W[r * 4 + 2] * tz + W[r * 4 + 3] * 1.0;
+}
+
+// bundle_position through an object record (mmba_object.hip): the parent's
+// world matrix comes from record set `set` of the observation -- the variant
+// of parameter p where p moves the parent at this frame, the base record
+// otherwise -- and the bundle's own translate from its attributes (where the
+// override lands for the bundle's own columns).  The same products and sums
+// as above on the same matrix entries.
+MMBA_DEV void orec_position(const DevProblem &P, const ObjRecDev &O, int b, int f, int set, int p,
+                            const Override &ov, double *pos) {
+    int slot = O.off[set];
+    if (p >= 0)
+        for (int q = slot + 1; q < O.off[set + 1]; ++q)
+            if (O.par[q] == p) slot = q;
+    const double *W = &O.rec[(size_t)slot * ORECSZ];
+    const int *ta = &P.tfm_attrs[9 * P.bnd_tfm[b]];
+    const double tx = attr_get(P, ta[0], f, 0., ov);
+    const double ty = attr_get(P, ta[1], f, 0., ov);
+    const double tz = attr_get(P, ta[2], f, 0., ov);
 #pragma unroll
     for (int r = 0; r < 3; ++r)
         pos[r] = W[r * 4 + 0] * tx + W[r * 4 + 1] * ty + W[r * 4 + 2] * tz + W[r * 4 + 3] * 1.0;

@@ -576,6 +576,8 @@ int group_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,
     return g.run(f);
 }
 
+const mmba_plan *group_first_plan(const mmba_plan *plan) { return plan->group->plans[0]; }
+
 // every shard joins the collectives; shard 0 writes the caller's arrays
 int group_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out) {
     ShardGroup &g = *plan->group;

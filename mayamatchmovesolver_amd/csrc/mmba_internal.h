@@ -35,6 +35,7 @@ constexpr int CAMREC = 20;  // doubles per camera-frame record
 constexpr int LENS_LAYER = 1 + MMBA_LENS_NUM_ATTRS;  // input lens layer: type, 14 slots
 constexpr int LENS_CHAIN_MAX = 4;                    // input layers per lens
 constexpr int BREC = 16;    // doubles per bundle record (128 B: one L2 line)
+constexpr int ORECSZ = 12;  // doubles per object record (a 3x4 world matrix)
 
 // In-place all-reduce of device buffers across the shards of a plan
 // (mmba_comm.cpp: RCCL, or an in-process group for tests).
@@ -268,7 +269,13 @@ enum ParamClass : int { PC_CF = 0, PC_B = 1, PC_G = 2 };
 // VF_LENS: the variant is a lens coefficient of the camera-frame (an
 // animated coefficient only its own camera-frame's rows read, Plan::build):
 // its camera record is the base one and its column perturbs the lens
-enum VarFlags : int { VF_BUNDLE_SIDE = 1, VF_LENS = 2 };
+// VF_OBJ: the variant is an object-frame parameter (an animated transform
+// above bundles, read at its frame by this camera-frame's rows only,
+// Plan::build), set together with VF_BUNDLE_SIDE, whose column it takes in
+// k_jacobian: its camera record repeats the base one (no camera attribute is
+// overridden) and its column moves the bundle; a row whose bundle is not
+// under the transform gets an exact zero
+enum VarFlags : int { VF_BUNDLE_SIDE = 1, VF_LENS = 2, VF_OBJ = 4 };
 
 // Device view of the problem + derived structure (all device pointers).
 struct DevProblem {
@@ -403,6 +410,24 @@ struct DevProblem {
     const int *ls_tab;
     double *ls_Aoff;
 };
+
+// Object records (mmba_object.hip): per (bundle-parent transform whose chain
+// holds an animated or solved attribute, frame with observations) one record
+// set -- slots [off[r], off[r + 1]): the parent's 3x4 world matrix at the
+// frame, then one variant per parameter that moves it there (par[slot], -1
+// for the base slot), ORECSZ doubles each in rec.  obs_set[i]: the set of
+// observation i (-1: its bundle takes the bundle record or the chain walk);
+// set[slot]: the slot's set; tf[2 r], tf[2 r + 1]: the set's transform and
+// frame.  n: slots (0: the plan has none).  Kept out of DevProblem: the
+// generic Jacobian kernel holds that struct in registers, and every field
+// added to it costs all its instantiations (the record-reading ones take
+// this struct as a kernel argument of their own).
+struct ObjRecDev {
+    int n = 0;
+    const int *obs_set = nullptr, *off = nullptr, *par = nullptr, *set = nullptr, *tf = nullptr;
+    double *rec = nullptr;
+};
+struct NoObjRec {};  // the argument of the instantiations that read no record
 
 __device__ __forceinline__ size_t widx(const DevProblem &P, int k, int i) {
     return (size_t)i * P.wst + k;

@@ -55,10 +55,29 @@ void launch_trial_prep(hipStream_t s, const DevProblem &P, const double *xs, con
                        double eps_dif, const int *mask, double *partial, int nparts,
                        int rstride);
 // Camera-frame records (variant 0 only when base_only) and bundle records,
-// one launch.
+// one launch; with O, the plan's object records behind them.
 void launch_records(hipStream_t s, const DevProblem &P, const int *var_cf,
                     const double *ext_pert, const double *step, double *recs, int nvar,
-                    double *brec, int base_only);
+                    double *brec, int base_only, const ObjRecDev *O = nullptr);
+// Object records (mmba_object.hip; launch_records calls it): every slot of
+// every record set at the attribute values now set, the variants with
+// ext_pert (base slots only when base_only).  No launch when O.n == 0.
+void launch_obj_records(hipStream_t s, const DevProblem &P, const ObjRecDev &O,
+                        const double *ext_pert, int base_only);
+// launch_residual / launch_residual_jp / launch_jacobian on a plan with
+// object records: the record-reading instantiations (mmba_object.hip; the
+// launchers above route here, reductions and dispatch stay theirs)
+void launch_residual_orec(hipStream_t s, const DevProblem &P, const ObjRecDev &O,
+                          const double *recs, double *f, double *eu, double *ed, double *partial,
+                          double *out, unsigned int *ticket, double *dist);
+void launch_residual_jp_orec(hipStream_t s, const DevProblem &P, const ObjRecDev &O,
+                             const double *recs, double *f, double *eu, double *ed,
+                             double *partial, const double *J, const int *jcol, const int *nloc,
+                             const double *pstep, double *partial_jp, double *dist);
+void launch_jacobian_orec(hipStream_t s, const DevProblem &P, const ObjRecDev &O,
+                          const double *recs, const double *ext_pert, const double *step,
+                          int solver_type, double *J, int *jcol, int *nloc,
+                          const int *stale_param, double *eu, double *ed);
 int residual_blocks(const DevProblem &P);
 // Partial count of the trial point's residual pass (launch_residual_jp):
 // one per camera-frame where trial_cf_fusable, else residual_blocks.
@@ -71,7 +90,8 @@ void launch_reproject(hipStream_t s, const DevProblem &P, const double *recs, do
                       double *mkr);
 void launch_residual(hipStream_t s, const DevProblem &P, const double *recs, double *f, double *eu,
                      double *ed, double *partial, double *out = nullptr,
-                     unsigned int *ticket = nullptr, double *dist = nullptr);
+                     unsigned int *ticket = nullptr, double *dist = nullptr,
+                     const ObjRecDev *O = nullptr);  // O: bundle positions through object records
 // errorDistanceList statistics (compute_error_stats) of ed: out[0] = sum of
 // the finite entries, out[1] = -min, out[2] = max (partial rows rstride apart)
 void launch_dist_stats(hipStream_t s, const DevProblem &P, const double *ed, double *partial,
@@ -81,7 +101,8 @@ void launch_dist_stats(hipStream_t s, const DevProblem &P, const double *ed, dou
 void launch_residual_jp(hipStream_t s, const DevProblem &P, const double *recs, double *f,
                         double *eu, double *ed, double *partial, const double *J,
                         const int *jcol, const int *nloc, const double *pstep,
-                        double *partial_jp, double *dist = nullptr);
+                        double *partial_jp, double *dist = nullptr,
+                        const ObjRecDev *O = nullptr);
 // Second evaluation of central FD columns (lmder, autoDiffType central):
 // records / bundle records / perturbed values at x + deltaB and the column
 // factor 0.5 / (|dA| + |dB|) (0: forward column).  recs == nullptr: forward.
@@ -131,7 +152,8 @@ void launch_jacobian(hipStream_t s, const DevProblem &P, const double *recs,
                      int *jcol, int *nloc, const int *stale_param, double *eu, double *ed,
                      int ncv = 0,  // ncv 6 / 7: uniform fast kernels (Plan::jac_ncv)
                      const double *f = nullptr,  // residuals at x (column-parallel kernel)
-                     const CentralB &CB = CentralB());
+                     const CentralB &CB = CentralB(),
+                     const ObjRecDev *O = nullptr);  // O: the record-reading instantiations
 // Attribute stiffness / smoothness rows (mmba_rows.hip): fr / eur point at
 // row 0 of the rows (f + 2M); partial[slot] gets the rows' sum of squares
 // (slot = nblk(M, 256): the entry after the residual blocks).

@@ -8,69 +8,14 @@
 //   everything else                  small O(n) vector work.
 #include <cfloat>
 #include <cstdlib>
+#include <type_traits>
 
 #include "mmba_geom.h"
 #include "mmba_kernels.h"
+#include "mmba_obs_dev.h"
 #include "mmba_red_dev.h"
 
 namespace mmba {
-
-// Frame-sharding ownership (all-true when unsharded).
-MMBA_DEV bool own_obs(const DevProblem &P, int i) { return !P.obs_own || P.obs_own[i]; }
-MMBA_DEV bool own_cf(const DevProblem &P, int cf) { return !P.cf_own || P.cf_own[cf]; }
-MMBA_DEV bool own_bnd(const DevProblem &P, int b) { return !P.bnd_own || P.bnd_own[b]; }
-MMBA_DEV bool own_mask(const int *m, int i) { return !m || m[i]; }
-
-// Workgroup b of a G-workgroup grid runs on XCD b mod 8; xcd_remap(b, G) is
-// the logical block it takes so that each XCD sweeps one contiguous range of
-// logical blocks (a bijection of [0, G)).  Kernels that walk the
-// camera-frame-sorted observations, the records they read and the Jacobian
-// they write use it alike, so a producer's lines sit in the L2 of the XCD
-// that reads them next.
-__device__ __forceinline__ int xcd_remap(int b, int G) {
-    const int x = b & 7, idx = b >> 3, q = G >> 3, r = G & 7;
-    return x * q + min(x, r) + idx;
-}
-
-// Deterministic single-launch reduction epilogue (see the reductions section).
-template <bool MAX>
-__device__ __forceinline__ void finish_blocks(double v, double *partial, double *out,
-                                              unsigned int *ticket, int blk = -1) {
-    if (blk < 0) blk = blockIdx.x;
-    __shared__ int last;
-    __shared__ double red[256];
-    if (threadIdx.x == 0) {
-        if (!ticket) {
-            partial[blk] = v;
-        } else {
-            __hip_atomic_store(&partial[blk], v, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            __threadfence();  // release the partial before the ticket
-            last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-        }
-    }
-    if (!ticket) return;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();  // acquire the other blocks' partials
-    double a = 0.;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += blockDim.x) {
-        const double q = __hip_atomic_load(&partial[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        a = MAX ? fmax(a, q) : a + q;
-    }
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w)
-            red[threadIdx.x] = MAX ? fmax(red[threadIdx.x], red[threadIdx.x + w])
-                                   : red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *out = red[0];
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
 
 // 3 x 3 damped bundle factor of one bundle (k_bundle_factor's arithmetic):
 // A (pb x pb block, identity padding), rhs = gB (0 on padding), dd = diag of
@@ -471,131 +416,6 @@ __global__ void __launch_bounds__(64) k_records(DevProblem P, const int *__restr
                           ext_pert, step, brec, base_only);
 }
 
-// -------------------------------------------------------------------------
-// Residuals (measureErrors).  Writes f (device order), user deviation and
-// distance, and one partial sum of squares per block.
-// -------------------------------------------------------------------------
-// JP: the trial-point evaluation also forms (J p)_obs = sum_l J_l p[jcol_l]
-// from the Jacobian blocks of the current x (lmder's ||J p|| for prered,
-// k_jp_sumsq) into a second partial row.
-// FAST: every bundle is fast and no camera has a lens (the transform-chain
-// and lens code, and their registers, are compiled out).
-// RS: rolling shutter (mmba_rs.hip): each observation's camera record is
-// its own scanline pose (camera_record_rs), not the camera-frame's.
-template <bool JP, bool FAST, bool RS = false>
-__global__ void __launch_bounds__(256) k_residual(DevProblem P, const double *__restrict__ recs,
-                                                  double *f, double *eu, double *ed,
-                                                  double *partial, double *out,
-                                                  unsigned int *ticket,
-                                                  const double *__restrict__ J,
-                                                  const int *__restrict__ jcol,
-                                                  const int *__restrict__ nloc,
-                                                  const double *__restrict__ pstep,
-                                                  double *partial_jp, double *dist) {
-    __shared__ double red[256];
-    const int lb = xcd_remap(blockIdx.x, gridDim.x);  // logical block (XCD-contiguous)
-    const int i = lb * blockDim.x + threadIdx.x;
-    double s = 0., sj = 0.;
-    if (i < P.M) {
-        const int cf = P.obs_cf[i];
-        const int b = P.obs_bnd[i];
-        const int fr = P.obs_frame[i];
-        const Override none{-1, 0.};
-        double bp[3];
-        if (FAST) {
-            const double *br = &P.brec[(size_t)b * BREC];
-            bp[0] = br[0];
-            bp[1] = br[1];
-            bp[2] = br[2];
-        } else {
-            base_bundle(P, b, fr, bp);
-        }
-        double lc[MMBA_LENS_NUM_ATTRS];
-        int inst = -1;
-        const int hl = FAST ? MMBA_LENS_NONE : obs_lens_inst(P, i, inst);
-        if (hl) inst_coeffs(P, inst, none, lc);
-        const double *rec = &recs[(size_t)P.cf_var_off[cf] * CAMREC];
-        double rloc[RS ? CAMREC : 1];
-        if constexpr (RS) {
-            camera_record_rs(P, cf, P.obs_tau[i], -1, 0., rloc);
-            rec = rloc;
-        }
-        Resid r = residual_l(P, rec, bp, P.obs_xy[2 * i], P.obs_xy[2 * i + 1], P.obs_sqrtw[i],
-                             hl, lc);
-        f[2 * i] = r.ex;
-        f[2 * i + 1] = r.ey;
-        if (eu) {
-            eu[2 * i] = r.ux;
-            eu[2 * i + 1] = r.uy;
-            ed[i] = r.dist;
-        }
-        if (dist) dist[i] = r.dist;  // errorDistanceList of this point (RMS at the accepted x)
-        if (own_obs(P, i)) {
-            s = r.ex * r.ex + r.ey * r.ey;
-            if constexpr (JP) {
-                const int M = P.M;
-                double ax = 0., ay = 0.;
-                const int nl = nloc[i];
-                if (P.jcol_implicit) {
-                    // uniform plans: column l is camera variant l (l < nv), then
-                    // the bundle's parameters (k_jacobian_u's order).  Eight
-                    // columns' index, step and J loads issued before their
-                    // products (the sums in column order as before)
-                    const int voff = P.cf_var_off[cf];
-                    const int nv = P.cf_var_off[cf + 1] - voff - 1;
-                    const int4 p4 = P.bnd_p4[b];
-                    for (int l0 = 0; l0 < nl; l0 += 8) {
-                        double jx[8], jy[8], pv[8];
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) {
-                            const int l = l0 + k;
-                            if (l < nl) {
-                                const int a = l - nv;
-                                const int p = l < nv ? P.cf_var_param[voff + 1 + l]
-                                                     : (a == 0 ? p4.x : (a == 1 ? p4.y : p4.z));
-                                pv[k] = pstep[p];
-                                jx[k] = J[(size_t)(2 * l) * M + i];
-                                jy[k] = J[(size_t)(2 * l + 1) * M + i];
-                            }
-                        }
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) {
-                            if (l0 + k < nl) {
-                                ax += jx[k] * pv[k];
-                                ay += jy[k] * pv[k];
-                            }
-                        }
-                    }
-                } else {
-                    for (int l = 0; l < nl; ++l) {
-                        const double pv = pstep[jcol[(size_t)l * M + i]];
-                        ax += J[(size_t)(2 * l) * M + i] * pv;
-                        ay += J[(size_t)(2 * l + 1) * M + i] * pv;
-                    }
-                }
-                sj = ax * ax + ay * ay;
-            }
-        }
-    }
-    if constexpr (JP) {
-        red[threadIdx.x] = sj;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partial_jp[lb] = red[0];
-        __syncthreads();
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    finish_blocks<false>(red[0], partial, out, ticket, lb);
-}
-
 // Trial point on uniform fast plans (one workgroup per camera-frame
 // segment, the plans of k_jac_ne_u): the camera-frame's base record and the
 // steps p of its camera parameters are staged once in LDS, where
@@ -684,211 +504,6 @@ __global__ void __launch_bounds__(256) k_residual_jp_cf(
     if (tid == 0) {
         partial[cf] = red[0][0];
         partial_jp[cf] = red[1][0];
-    }
-}
-
-// -------------------------------------------------------------------------
-// FD Jacobian blocks per observation (K1/K2 in SURVEY 7): same differences
-// as solveFunc_calculateJacobianMatrixForParameter, evaluated only for the
-// parameters that can change this observation (all other entries of the
-// reference column are exactly zero).
-// -------------------------------------------------------------------------
-// CEN: central differences / B15 compiled in (CB.recs != nullptr).  The
-// forward-difference build drops the deltaB evaluations and is held to two
-// waves per SIMD (256 VGPRs, some spilled; one wave at 340 registers before):
-// C5 1.21 against 1.33 ms per solve (profiles/r5_jac/).
-template <bool CEN, int LT = -1>
-__global__ void __launch_bounds__(128, CEN ? 1 : 2) k_jacobian(DevProblem P, const double *__restrict__ recs,
-                                                  const double *__restrict__ ext_pert,
-                                                  const double *__restrict__ step,
-                                                  int solver_type, double *J, int *jcol,
-                                                  int *nloc, const int *__restrict__ stale_param,
-                                                  double *eu, double *ed, CentralB CB) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= P.M) return;
-    const int M = P.M;
-    const int cf = P.obs_cf[i];
-    const int b = P.obs_bnd[i];
-    const int fr = P.obs_frame[i];
-    const double mx = P.obs_xy[2 * i], my = P.obs_xy[2 * i + 1], sw = P.obs_sqrtw[i];
-    const Override none{-1, 0.};
-    const int4 p4 = P.bnd_p4[b];
-    double bp0[3];
-    base_bundle(P, b, fr, bp0);
-    double lc0[MMBA_LENS_NUM_ATTRS];
-    int inst = -1;
-    const int hl = obs_lens_inst(P, i, inst);
-    if (hl) inst_coeffs(P, inst, none, lc0);
-    const int voff = P.cf_var_off[cf];
-    const int nvar = P.cf_var_off[cf + 1] - voff;
-    const double *rec0 = &recs[(size_t)voff * CAMREC];
-    const Resid r0 = residual_l<LT>(P, rec0, bp0, mx, my, sw, hl, lc0);
-    const bool lmder = solver_type == MMBA_SOLVER_CMINPACK_LMDER;
-    const int pstale = stale_param[fr];
-    Resid rs = r0;
-    int l = 0;
-    double ljx = 0., ljy = 0.;  // last emitted column (bundle block record)
-    // evalB: the column's second (deltaB) evaluation, run only for a central
-    // column (CB.step[p] != 0)
-    auto emit_s = [&](int p, const Resid &r, double st, auto &&evalB) {
-        double jx, jy;
-        const double sB = (CEN && lmder && CB.recs) ? CB.step[p] : 0.;
-        if (sB != 0.) {  // central: (f(x + dA) - f(x + dB)) * 0.5 / (|dA| + |dB|)
-            const Resid rb = evalB();
-            jx = (r.ex - rb.ex) * sB;
-            jy = (r.ey - rb.ey) * sB;
-            if (p == pstale) rs = rb;  // the column's last measureErrors
-        } else {
-            if (lmder) {  // st = 1/delta, multiplied (adjust_solveFunc.cpp:395-402)
-                jx = (r.ex - r0.ex) * st;
-                jy = (r.ey - r0.ey) * st;
-            } else {      // st = h, divided (fdjac2)
-                jx = (r.ex - r0.ex) / st;
-                jy = (r.ey - r0.ey) / st;
-            }
-            if (p == pstale) rs = r;
-        }
-        J[(size_t)(2 * l) * M + i] = jx;
-        J[(size_t)(2 * l + 1) * M + i] = jy;
-        jcol[(size_t)l * M + i] = p;
-        ljx = jx;
-        ljy = jy;
-        ++l;
-    };
-    // camera-side parameters (variants 1..nvar-1)
-    for (int v = 1; v < nvar && l < LMAX; ++v) {
-        const int t = voff + v;
-        const int p = P.cf_var_param[t];
-        const bool bside = (P.cf_var_flags[t] & VF_BUNDLE_SIDE) != 0;
-        if (P.cf_var_flags[t] & VF_LENS) {
-            // a lens coefficient in the camera-frame block: the lens loop's
-            // column (below), at its place in the block -- where this
-            // observation's lens instance holds the coefficient (B3 may give
-            // it an instance another frame's parameter wrote: then f - f = 0)
-            bool holds = false;
-            if (hl)
-                for (int q = P.inst_lpar_off[inst]; q < P.inst_lpar_off[inst + 1]; ++q)
-                    holds |= P.inst_lpar[q] == p;
-            double lc[MMBA_LENS_NUM_ATTRS];
-            if (holds) inst_coeffs(P, inst, Override{P.p_attr[p], ext_pert[p]}, lc);
-            emit_s(p, residual_l<LT>(P, rec0, bp0, mx, my, sw, hl, holds ? lc : lc0), step[p], [&]() {
-                double lq[MMBA_LENS_NUM_ATTRS];
-                if (holds) inst_coeffs(P, inst, Override{P.p_attr[p], CB.ext_pert[p]}, lq);
-                return residual_l<LT>(P, rec0, bp0, mx, my, sw, hl, holds ? lq : lc0);
-            });
-            continue;
-        }
-        double bp[3] = {bp0[0], bp0[1], bp0[2]};
-        if (bside) bundle_position(P, b, fr, Override{P.p_attr[p], ext_pert[p]}, bp);
-        emit_s(p, residual_l<LT>(P, &recs[(size_t)t * CAMREC], bp, mx, my, sw, hl, lc0), step[p],
-               [&]() {
-                   double bq[3] = {bp0[0], bp0[1], bp0[2]};
-                   if (bside) bundle_position(P, b, fr, Override{P.p_attr[p], CB.ext_pert[p]}, bq);
-                   return residual_l<LT>(P, &CB.recs[(size_t)t * CAMREC], bq, mx, my, sw, hl, lc0);
-               });
-    }
-    if (CEN && CB.q15) {
-        // B15 (Plan::b15): the camera-frame block's columns (the first pc
-        // emitted) in the basis Q_cf (Q c = kappa e_0): J_s Q = J Q - f kappa
-        // e_0^T with J the central differences of the block's own frame.  The
-        // large f c part of the block lands in one column, so the block's
-        // normal equations keep the accuracy of its differences.
-        const int pc = P.cf_pc[cf];
-        const double *Q = CB.q15 + (size_t)cf * PCMAX * PCMAX;
-        const double kap = CB.kap15[cf];
-        double ax[PCMAX], ay[PCMAX];
-#pragma unroll
-        for (int a = 0; a < PCMAX; ++a) {
-            ax[a] = a < pc ? J[(size_t)(2 * a) * M + i] : 0.;
-            ay[a] = a < pc ? J[(size_t)(2 * a + 1) * M + i] : 0.;
-        }
-#pragma unroll
-        for (int a2 = 0; a2 < PCMAX; ++a2) {
-            if (a2 >= pc) break;
-            double sx = 0., sy = 0.;
-#pragma unroll
-            for (int a = 0; a < PCMAX; ++a) {
-                sx = fma(ax[a], Q[a * PCMAX + a2], sx);
-                sy = fma(ay[a], Q[a * PCMAX + a2], sy);
-            }
-            if (a2 == 0) {
-                sx -= r0.ex * kap;
-                sy -= r0.ey * kap;
-            }
-            J[(size_t)(2 * a2) * M + i] = sx;
-            J[(size_t)(2 * a2 + 1) * M + i] = sy;
-        }
-    }
-    // bundle-side parameters not already covered by a camera variant
-    if (p4.w >= 0) {  // fast bundle: perturbed positions from the record
-        const double *br = &P.brec[(size_t)b * BREC];
-        double jb[8] = {0., 0., 0., 0., 0., 0., r0.ex, r0.ey};
-        for (int a = 0; a < p4.w && l < LMAX; ++a) {
-            const int p = a == 0 ? p4.x : (a == 1 ? p4.y : p4.z);
-            const double bp[3] = {br[3 + 3 * a], br[4 + 3 * a], br[5 + 3 * a]};
-            emit_s(p, residual_l<LT>(P, rec0, bp, mx, my, sw, hl, lc0), br[12 + a], [&]() {
-                const double *bb = &CB.brec[(size_t)b * BREC];
-                const double bq[3] = {bb[3 + 3 * a], bb[4 + 3 * a], bb[5 + 3 * a]};
-                return residual_l<LT>(P, rec0, bq, mx, my, sw, hl, lc0);
-            });
-            jb[2 * a] = ljx;
-            jb[2 * a + 1] = ljy;
-        }
-        // bundle block record, one 64-B record per observation (coalesced
-        // store; k_ne_bnd_jb gathers one record per observation of a bundle
-        // instead of 8 SoA rows): [jx_a, jy_a]_a, f_x, f_y
-        if (P.JB) {
-            double4 *dst = reinterpret_cast<double4 *>(&P.JB[(size_t)P.obs_bpos[i] * 8]);
-            dst[0] = make_double4(jb[0], jb[1], jb[2], jb[3]);
-            dst[1] = make_double4(jb[4], jb[5], jb[6], jb[7]);
-        }
-    }
-    for (int q = p4.w >= 0 ? P.bnd_par_off[b + 1] : P.bnd_par_off[b];
-         q < P.bnd_par_off[b + 1] && l < LMAX; ++q) {
-        const int p = P.bnd_par[q];
-        if (P.p_frame[p] >= 0 && P.p_frame[p] != fr) continue;
-        if (P.p_both[p]) {
-            bool seen = false;
-            for (int v = 1; v < nvar; ++v) seen |= (P.cf_var_param[voff + v] == p);
-            if (seen) continue;
-        }
-        double bp[3];
-        bundle_position(P, b, fr, Override{P.p_attr[p], ext_pert[p]}, bp);
-        emit_s(p, residual_l<LT>(P, rec0, bp, mx, my, sw, hl, lc0), step[p], [&]() {
-            double bq[3];
-            bundle_position(P, b, fr, Override{P.p_attr[p], CB.ext_pert[p]}, bq);
-            return residual_l<LT>(P, rec0, bq, mx, my, sw, hl, lc0);
-        });
-    }
-    // the lens parameters this observation's lens instance holds (an
-    // instance slot has one attribute, so overriding by attribute moves only
-    // the slot the parameter writes)
-    if (hl) {
-        for (int q = P.inst_lpar_off[inst]; q < P.inst_lpar_off[inst + 1] && l < LMAX; ++q) {
-            const int p = P.inst_lpar[q];
-            // an animated parameter's column re-measures its own frame only
-            // (adjust_solveFunc.cpp frameIndexEnable): the observations of
-            // other frames that read the instance it writes keep f - f = 0
-            if (P.p_frame[p] >= 0 && P.p_frame[p] != fr) continue;
-            // a camera-frame block column (VF_LENS) of this row's own block;
-            // another camera-frame's block hosts a coefficient several cameras
-            // read (mmba_lens_shared.hip): a foreign row emits its column here
-            if (P.p_class[p] == PC_CF && P.p_blk[p] == cf) continue;
-            double lc[MMBA_LENS_NUM_ATTRS];
-            inst_coeffs(P, inst, Override{P.p_attr[p], ext_pert[p]}, lc);
-            emit_s(p, residual_l<LT>(P, rec0, bp0, mx, my, sw, hl, lc), step[p], [&]() {
-                double lq[MMBA_LENS_NUM_ATTRS];
-                inst_coeffs(P, inst, Override{P.p_attr[p], CB.ext_pert[p]}, lq);
-                return residual_l<LT>(P, rec0, bp0, mx, my, sw, hl, lq);
-            });
-        }
-    }
-    nloc[i] = l;
-    // errorList / errorDistanceList as left by the last FD column (Appendix B13).
-    if (eu) {
-        eu[2 * i] = rs.ux;
-        eu[2 * i + 1] = rs.uy;
-        ed[i] = rs.dist;
     }
 }
 
@@ -4103,12 +3718,13 @@ void launch_param_prep(hipStream_t s, const DevProblem &P, const double *x, doub
 }
 void launch_records(hipStream_t s, const DevProblem &P, const int *var_cf,
                     const double *ext_pert, const double *step, double *recs, int nvar,
-                    double *brec, int base_only) {
+                    double *brec, int base_only, const ObjRecDev *O) {
     const int ncb = (nblk(base_only ? P.ncf : nvar, 64) + 7) / 8 * 8;  // see k_records
     const int nbb = nblk(P.nB, 64);
     if (ncb + nbb > 0)
         k_records<<<ncb + nbb, 64, 0, s>>>(P, var_cf, ext_pert, step, recs, nvar, brec, base_only,
                                            ncb);
+    if (O) launch_obj_records(s, P, *O, ext_pert, base_only);  // ... of the same point
 }
 void launch_param_set(hipStream_t s, const DevProblem &P, const double *x, double *ext,
                       double *ext_pert, double *step, int solver_type, double delta,
@@ -4162,7 +3778,8 @@ bool &trial_cf_off() {  // the per-256-observation kernel instead (tests set it)
 }
 int trial_blocks(const DevProblem &P) { return trial_cf_fusable(P) ? P.ncf : residual_blocks(P); }
 void launch_residual(hipStream_t s, const DevProblem &P, const double *recs, double *f, double *eu,
-                     double *ed, double *partial, double *out, unsigned int *ticket, double *dist) {
+                     double *ed, double *partial, double *out, unsigned int *ticket, double *dist,
+                     const ObjRecDev *O) {
     // the ticket epilogue sums the residual kernel's own nblk(M) partials
     // only: with stiffness / smoothness rows (one more partial, k_rows_eval)
     // the two-launch reduction runs
@@ -4170,15 +3787,17 @@ void launch_residual(hipStream_t s, const DevProblem &P, const double *recs, dou
     if (P.rs)
         k_residual<false, false, true><<<nblk(P.M, 256), 256, 0, s>>>(
             P, recs, f, eu, ed, partial, out, ticket, nullptr, nullptr, nullptr, nullptr, nullptr,
-            dist);
+            dist, NoObjRec{});
     else if (P.all_bnd_fast && P.no_lens)
         k_residual<false, true><<<nblk(P.M, 256), 256, 0, s>>>(
             P, recs, f, eu, ed, partial, out, ticket, nullptr, nullptr, nullptr, nullptr, nullptr,
-            dist);
+            dist, NoObjRec{});
+    else if (O && O->n > 0)  // object records (mmba_object.hip)
+        launch_residual_orec(s, P, *O, recs, f, eu, ed, partial, out, ticket, dist);
     else
         k_residual<false, false><<<nblk(P.M, 256), 256, 0, s>>>(
             P, recs, f, eu, ed, partial, out, ticket, nullptr, nullptr, nullptr, nullptr, nullptr,
-            dist);
+            dist, NoObjRec{});
     if (!ticket && out) k_reduce_sum<<<1, 256, 0, s>>>(partial, residual_blocks(P), out);
 }
 // Per-observation reprojection (FlatScene::evaluate's out_point_list /
@@ -4217,7 +3836,7 @@ void launch_reproject(hipStream_t s, const DevProblem &P, const double *recs, do
 void launch_residual_jp(hipStream_t s, const DevProblem &P, const double *recs, double *f,
                         double *eu, double *ed, double *partial, const double *J,
                         const int *jcol, const int *nloc, const double *pstep,
-                        double *partial_jp, double *dist) {
+                        double *partial_jp, double *dist, const ObjRecDev *O) {
     if (trial_cf_fusable(P)) {  // partials per camera-frame (trial_blocks)
         if (P.pc_uniform == 6)
             k_residual_jp_cf<6><<<P.ncf, 256, 0, s>>>(P, recs, f, eu, ed, partial, J, nloc, pstep,
@@ -4229,13 +3848,19 @@ void launch_residual_jp(hipStream_t s, const DevProblem &P, const double *recs, 
     }
     if (P.rs)
         k_residual<true, false, true><<<nblk(P.M, 256), 256, 0, s>>>(
-            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist);
+            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist,
+            NoObjRec{});
     else if (P.all_bnd_fast && P.no_lens)
         k_residual<true, true><<<nblk(P.M, 256), 256, 0, s>>>(
-            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist);
+            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist,
+            NoObjRec{});
+    else if (O && O->n > 0)  // object records (mmba_object.hip)
+        launch_residual_jp_orec(s, P, *O, recs, f, eu, ed, partial, J, jcol, nloc, pstep, partial_jp,
+                                dist);
     else
         k_residual<true, false><<<nblk(P.M, 256), 256, 0, s>>>(
-            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist);
+            P, recs, f, eu, ed, partial, nullptr, nullptr, J, jcol, nloc, pstep, partial_jp, dist,
+            NoObjRec{});
 }
 
 // compute_error_stats (adjust_base.cpp:346-372) on the device: per block the
@@ -4311,7 +3936,7 @@ void launch_dist_stats(hipStream_t s, const DevProblem &P, const double *ed, dou
 void launch_jacobian(hipStream_t s, const DevProblem &P, const double *recs,
                      const double *ext_pert, const double *step, int solver_type, double *J,
                      int *jcol, int *nloc, const int *stale_param, double *eu, double *ed,
-                     int ncv, const double *f, const CentralB &CB) {
+                     int ncv, const double *f, const CentralB &CB, const ObjRecDev *O) {
     (void)f;
     if (P.rs) {  // rolling shutter: three camera-frame blocks per row (mmba_rs.hip)
         launch_jacobian_rs(s, P, ext_pert, step, solver_type, J, jcol, nloc, stale_param, eu, ed);
@@ -4339,13 +3964,19 @@ void launch_jacobian(hipStream_t s, const DevProblem &P, const double *recs,
 #undef MMBA_JAC_U
     if (CB.recs)
         k_jacobian<true><<<nblk(P.M, 128), 128, 0, s>>>(P, recs, ext_pert, step, solver_type, J,
-                                                      jcol, nloc, stale_param, eu, ed, CB);
+                                                      jcol, nloc, stale_param, eu, ed, CB,
+                                                      NoObjRec{});
+    else if (O && O->n > 0)  // object records (mmba_object.hip)
+        launch_jacobian_orec(s, P, *O, recs, ext_pert, step, solver_type, J, jcol, nloc,
+                             stale_param, eu, ed);
     else if (P.lens_uniform == MMBA_LENS_3DE_CLASSIC)  // C5: the classic model only
         k_jacobian<false, MMBA_LENS_3DE_CLASSIC><<<nblk(P.M, 128), 128, 0, s>>>(
-            P, recs, ext_pert, step, solver_type, J, jcol, nloc, stale_param, eu, ed, CB);
+            P, recs, ext_pert, step, solver_type, J, jcol, nloc, stale_param, eu, ed, CB,
+                                                      NoObjRec{});
     else
         k_jacobian<false><<<nblk(P.M, 128), 128, 0, s>>>(P, recs, ext_pert, step, solver_type, J,
-                                                       jcol, nloc, stale_param, eu, ed, CB);
+                                                       jcol, nloc, stale_param, eu, ed, CB,
+                                                      NoObjRec{});
 }
 // One workgroup per camera-frame only fills the chip with enough
 // camera-frames (C4: 500 x 400 observations); a few long segments (C2: 120 x

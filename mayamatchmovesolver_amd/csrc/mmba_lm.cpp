@@ -250,7 +250,7 @@ double Plan::dnorm(const double *dv) {
 }
 
 void Plan::records_enqueue(const double *xat, int base_only) {
-    launch_records(s, P, d_var_cf, d_ext_pert, d_step, d_recs, nvar, d_brec, base_only);
+    launch_records(s, P, d_var_cf, d_ext_pert, d_step, d_recs, nvar, d_brec, base_only, &orec);
     recs_full_at = base_only ? nullptr : xat;
 }
 
@@ -272,7 +272,7 @@ void Plan::fun_enqueue(const double *dx, double *df, double *eu, double *ed, dou
     // the ticket epilogue sums only the residual kernel's own grid: with
     // attribute rows the rows' partial would be dropped, so reduce separately
     launch_residual(s, P, d_recs, df, eu, ed, d_partial, d_scalar + slot,
-                    P.nrows > 0 ? nullptr : d_ticket, dist);
+                    P.nrows > 0 ? nullptr : d_ticket, dist, &orec);
     span_end(SPAN_RESID);
     allreduce(d_scalar + slot, 1);
 }
@@ -514,7 +514,7 @@ void Plan::jac(const double *dx, const JacLM *lm) {
         nloc_set = true;
     } else {
         launch_jacobian(s, P, d_recs, d_ext_pert, d_step, opt.solver_type, d_J, d_jcol, d_nloc,
-                        d_stale, d_eu, d_ed, jac_ncv, d_f, CB);
+                        d_stale, d_eu, d_ed, jac_ncv, d_f, CB, &orec);
     }
     if (k2_fused) epi_jb(*this, epi);
     launch_rows_jac(s, P, d_ext, d_ext_pert, d_step, central ? d_ext_pertB : nullptr,
@@ -618,7 +618,7 @@ void Plan::trial_enqueue(double *eu, double *ed, bool with_dnorm, bool fill_dnor
     // which the reduction's last block mirrors to the host itself
     const bool mirror = host_mirror && nranks == 1;
     launch_residual_jp(s, P, d_recs, d_ftrial, eu, ed, pr + 2 * (size_t)pw, d_J, d_jcol, d_nloc,
-                       b15 ? d_p15 : d_wa1, pr + 3 * (size_t)pw, d_dist_t);
+                       b15 ? d_p15 : d_wa1, pr + 3 * (size_t)pw, d_dist_t, &orec);
     span_end(SPAN_RESID);
     LmDec D;
     if (dec) {
@@ -1290,7 +1290,8 @@ int Plan::measure(const double *x, double *fvec_out, double *eu_out, double *ed_
         records_enqueue(nullptr, 1);
         launch_rows_eval(s, P, d_f + 2 * (size_t)M, d_eu + 2 * (size_t)M, d_partial,
                          (M + 255) / 256);
-        launch_residual(s, plug_problem(), d_recs, d_f, d_eu, d_ed, d_partial);
+        launch_residual(s, plug_problem(), d_recs, d_f, d_eu, d_ed, d_partial, nullptr, nullptr,
+                        nullptr, &orec);
     }
     if (nranks > 1) {
         // sharded: the statistics all-reduced, the outputs handed back by
@@ -1568,7 +1569,7 @@ void Plan::jac_partial_stale(const double *dx, int k) {
     }
     // the generic kernel honours the stale table for every column
     launch_jacobian(s, P, d_recs, d_ext_pert, d_step, opt.solver_type, d_J, d_jcol, d_nloc,
-                    d_stale, d_eu, d_ed, 0, d_f, CB);
+                    d_stale, d_eu, d_ed, 0, d_f, CB, &orec);
     launch_rows_jac(s, P, d_ext, d_ext_pert, d_step, central ? d_ext_pertB : nullptr,
                     central ? d_stepB : nullptr, lmdif ? 0 : 1, d_Jrow, d_eu + 2 * (size_t)M,
                     k - 1);
@@ -1659,7 +1660,7 @@ int Plan::solve_once(double *x_inout, double *fvec_out, double *eu_out, double *
         launch_rows_eval(s, P, d_f + 2 * (size_t)M, d_eu + 2 * (size_t)M, d_partial,
                          (M + 255) / 256);
         launch_residual(s, plug_problem(), d_recs, d_f, d_eu, d_ed, d_partial, d_scalar + SL_FI,
-                        nullptr, d_dist_x);
+                        nullptr, d_dist_x, &orec);
         allreduce(d_scalar + SL_FI, 1);
         error_stats_enqueue(d_ed, SL_IESUM);
         measured = true;

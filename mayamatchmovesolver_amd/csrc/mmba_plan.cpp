@@ -599,11 +599,70 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         auto it = cf_id.lower_bound({pr->param_frame[p], INT32_MIN});  // lens_cam -2: no reader
         return (it != cf_id.end() && it->first.first == pr->param_frame[p]) ? it->first.second : -1;
     };
+    // ---- an object-frame parameter: an animated transform attribute above
+    // bundles and above no camera (a rigid object keyed per frame, its
+    // bundles parented under it).  Its column re-measures its own frame only
+    // (frameIndexEnable, as above), so it reaches the rows of that frame whose
+    // bundle hangs under the transform.  Read there by ONE camera it joins
+    // that camera-frame's block (VF_OBJ) instead of the global arrow; read by
+    // no row (the object unseen at the frame: a zero column) it is hosted by
+    // the frame's first camera-frame, as the shared lens form hosts its
+    // unread coefficients; read by several cameras it stays global.  Taken
+    // where the global form would exceed NGMAX (MMBA_PATH_OBJ_CF = 1: wherever
+    // eligible, 0: never).  Forward differences, no rolling shutter, no
+    // robust loss, one device ----
+    std::vector<int> obj_cam(n, -3);  // -3: no such parameter, -2: no reader, -1: several cameras
+    bool has_obj = false, obj_several = false;
+    for (int p = 0; p < n; ++p) {
+        const int a = pr->param_attr[p];
+        if (pr->param_frame[p] >= 0 && attr_lcams[a].empty() && attr_cams[a].empty() &&
+            !attr_bnds[a].empty()) {
+            obj_cam[p] = -2;
+            has_obj = true;
+        }
+    }
+    const int obj_pin = path_choice(MMBA_PATH_OBJ_CF);
+    const char *obj_off = nullptr;  // the condition that keeps them global
+    if (obj_pin == 0) obj_off = "MMBA_PATH_OBJ_CF = 0";
+    else if (rs_on) obj_off = "rolling shutter";
+    else if (central) obj_off = "central differences";
+    else if (opt.robust_loss) obj_off = "robust loss";
+    else if (nranks > 1) obj_off = "sharded plan";
+    if (has_obj && !obj_off) {
+        require(M == Mg, "object classification before sharding");
+        std::vector<std::vector<int>> frame_obs(F);
+        for (int r = 0; r < Mg; ++r) frame_obs[pr->obs_frame[r]].push_back(r);
+        std::map<int, std::vector<char>> under;  // attribute -> its bundles, as a mask
+        for (int p = 0; p < n; ++p) {
+            if (obj_cam[p] == -3) continue;
+            const int a = pr->param_attr[p];
+            auto it = under.find(a);
+            if (it == under.end()) {
+                it = under.emplace(a, std::vector<char>(nB, 0)).first;
+                for (int b : attr_bnds[a]) it->second[b] = 1;
+            }
+            for (int r : frame_obs[pr->param_frame[p]]) {
+                if (!it->second[pr->mkr_bnd[obs_geo[r]]]) continue;
+                int &c = obj_cam[p];
+                c = c == -2 ? obs_cam[r] : (c == obs_cam[r] ? c : -1);
+            }
+            if (obj_cam[p] == -1) obj_several = true;
+        }
+    }
+    // the camera whose camera-frame hosts an object-frame parameter, -1: global
+    auto obj_host = [&](int p) -> int {
+        if (obj_cam[p] >= 0) return obj_cam[p];
+        if (obj_cam[p] != -2) return -1;
+        auto it = cf_id.lower_bound({pr->param_frame[p], INT32_MIN});
+        return (it != cf_id.end() && it->first.first == pr->param_frame[p]) ? it->first.second : -1;
+    };
     // ---- classify parameters ----
     std::vector<int> p_class(n), p_blk(n, -1), p_pos(n, -1), p_both(n, 0), p_lens(n, 0);
     std::vector<int> p_shared(n, 0);  // hosted in the shared form
+    std::vector<int> p_obj(n, 0);     // an object-frame parameter in a camera-frame block
     std::vector<std::pair<int, int>> p_cfkey(n, {-1, -1});
     lens_shared = false;
+    bool obj_form = false;  // object-frame parameters join the blocks
     // shared: the several-camera form too; returns the number of globals
     auto classify = [&](bool shared) -> int {
         int ng = 0;
@@ -632,6 +691,10 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
                 p_shared[p] = 1;
                 p_cfkey[p] = {fp, shared_host(p)};
                 if (lens_cam[p] == -1) lens_shared = true;
+            } else if (obj_form && obj_host(p) >= 0) {
+                p_class[p] = PC_CF;
+                p_obj[p] = 1;
+                p_cfkey[p] = {fp, obj_host(p)};
             } else {
                 p_class[p] = PC_G;
                 ++ng;
@@ -639,9 +702,13 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         }
         return ng;
     };
-    // the forms taken so far first; the shared form where they leave more
-    // than NGMAX globals, or where it is pinned on
-    const int ng_plain = classify(false);
+    // the forms taken so far first; the object form and the shared form
+    // where they leave more than NGMAX globals, or where they are pinned on
+    int ng_plain = classify(false);
+    if (has_obj && !obj_off && (obj_pin == 1 || ng_plain > NGMAX)) {
+        obj_form = true;
+        ng_plain = classify(false);
+    }
     if (!shared_off && has_anim_lens && !inst_lens_h.empty() &&
         (shared_pin == 1 || ng_plain > NGMAX))
         classify(true);
@@ -707,6 +774,16 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
                                ? std::string(" (animated lens coefficients shared by several "
                                              "cameras stay global parameters: ") +
                                      shared_off + ")"
+                               : std::string()) +
+                          (has_obj && obj_off
+                               ? std::string(" (animated transforms above bundles stay global "
+                                             "parameters: ") +
+                                     obj_off + ")"
+                               : std::string()) +
+                          (obj_form && obj_several
+                               ? std::string(" (an animated transform above bundles seen by "
+                                             "several cameras at one frame stays a global "
+                                             "parameter per frame)")
                                : std::string())};
     for (int q = 0; q < nG; ++q) p_pos[g_param[q]] = nCF + q;
     nR = nCF + nG;
@@ -720,7 +797,9 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         var_cf.push_back(cf);
         for (int p : cf_params[cf]) {
             cf_var_param.push_back(p);
-            cf_var_flags.push_back(p_lens[p] ? VF_LENS : (p_both[p] ? VF_BUNDLE_SIDE : 0));
+            cf_var_flags.push_back(p_lens[p]  ? VF_LENS
+                                   : p_obj[p] ? (VF_OBJ | VF_BUNDLE_SIDE)
+                                              : (p_both[p] ? VF_BUNDLE_SIDE : 0));
             var_cf.push_back(cf);
         }
         for (int p : g_param) {
@@ -975,8 +1054,11 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     };
     auto obs_cols = [&](int i) {
         const int cf = d_cf[i];
-        int nl = (cf_var_off[cf + 1] - cf_var_off[cf] - 1) +
-                 (bnd_par_off[d_bnd[i] + 1] - bnd_par_off[d_bnd[i]]) + lens_cols(i);
+        int nl = (cf_var_off[cf + 1] - cf_var_off[cf] - 1) + lens_cols(i);
+        // the bundle-side parameters valid at the observation's frame (an
+        // animated one emits its column in its own frame's rows only)
+        for (int t = bnd_par_off[d_bnd[i]]; t < bnd_par_off[d_bnd[i] + 1]; ++t)
+            if (pr->param_frame[bnd_par[t]] < 0 || pr->param_frame[bnd_par[t]] == d_frame[i]) ++nl;
         for (int side = 0; side < 2; ++side)
             if (cf_nb[2 * cf + side] >= 0) nl += cf_pc[cf_nb[2 * cf + side]];
         return nl;
@@ -1630,6 +1712,77 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         D.ls_Aoff = dalloc<double>((size_t)D.ls_nl * PCMAX * PCMAX);
         MMBA_HIP(hipMemsetAsync(D.ls_Aoff, 0, sizeof(double) * D.ls_nl * PCMAX * PCMAX, s));
     }
+    // object records (mmba_object.hip): the world matrix of every bundle
+    // parent whose chain an animated or solved attribute moves, once per
+    // evaluation and frame instead of once per observation and column.  Where
+    // the generic kernels run (k_jacobian / k_residual; the uniform kernels
+    // keep the chain walk), forward differences, no rolling shutter, one device
+    orec = ObjRecDev();
+    obj_rec_moved = false;
+    const int rec_pin = path_choice(MMBA_PATH_OBJ_REC);
+    if ((rec_pin < 0 ? kObjRecDefault : rec_pin != 0) && !rs_on && !central && nranks == 1 &&
+        jac_ncv == 0) {
+        std::vector<std::vector<int>> attr_params(nA);
+        for (int p = 0; p < n; ++p) attr_params[pr->param_attr[p]].push_back(p);
+        // the parameters of each transform's chain (ascending), and whether
+        // anything moves the chain at all
+        std::vector<int> moves(nT, -1);
+        auto chain_moves = [&](int t) -> bool {
+            if (moves[t] < 0) {
+                moves[t] = 0;
+                for (int u : chain[t])
+                    for (int k = 0; k < 9; ++k) {
+                        const int a = pr->tfm_attrs[9 * u + k];
+                        if (a >= 0 && (pr->attr_animated[a] || !attr_params[a].empty())) moves[t] = 1;
+                    }
+            }
+            return moves[t] == 1;
+        };
+        std::map<std::pair<int, int>, int> set_id;
+        std::vector<int> obs_orec(M, -1), tf;
+        for (int i = 0; i < M; ++i) {
+            const int b = d_bnd[i];
+            const int t = pr->tfm_parent[pr->bnd_tfm[b]];
+            if (bnd_p4[b].w >= 0 || t < 0 || !chain_moves(t)) continue;
+            auto ins = set_id.emplace(std::make_pair(t, d_frame[i]), (int)set_id.size());
+            if (ins.second) {
+                tf.push_back(t);
+                tf.push_back(d_frame[i]);
+            }
+            obs_orec[i] = ins.first->second;
+        }
+        const int nset = (int)set_id.size();
+        if (nset > 0) {
+            std::vector<int> off(nset + 1, 0), par, set;
+            for (int r = 0; r < nset; ++r) {
+                off[r] = (int)par.size();
+                par.push_back(-1);
+                set.push_back(r);
+                std::set<int> ps;
+                for (int u : chain[tf[2 * r]])
+                    for (int k = 0; k < 9; ++k) {
+                        const int a = pr->tfm_attrs[9 * u + k];
+                        if (a < 0) continue;
+                        for (int p : attr_params[a])
+                            if (pr->param_frame[p] < 0 || pr->param_frame[p] == tf[2 * r + 1])
+                                ps.insert(p);
+                    }
+                for (int p : ps) {
+                    par.push_back(p);
+                    set.push_back(r);
+                }
+            }
+            off[nset] = (int)par.size();
+            obj_rec_moved = (int)par.size() > nset;
+            orec.n = (int)par.size();
+            orec.obs_set = upload(obs_orec);
+            orec.off = upload(off);
+            orec.par = upload(par);
+            orec.set = upload(set);
+            orec.tf = upload(tf);
+            orec.rec = dalloc<double>((size_t)orec.n * ORECSZ);
+        }
+    }
     D.loss_on = opt.robust_loss ? 1 : 0;
     D.loss_type = opt.robust_loss_type;
     D.loss_scale = opt.robust_loss_scale;
@@ -1652,6 +1805,8 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         D.bnd_own = upload(bown);
         d_p_own = upload(p_own);
     }
+    p_class_h = p_class;
+    p_blk_h = p_blk;
     P = D;
     if (rs_bnd) {
         PV = P;
@@ -1878,6 +2033,8 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         if (!why && nranks != 1) why = "sharded plan";
         for (int p = 0; p < n && !why; ++p)
             if (p_lens[p]) why = "a lens coefficient in a camera-frame block";
+        for (int p = 0; p < n && !why; ++p)
+            if (p_obj[p]) why = "an object transform parameter in a camera-frame block";
         if (!why && nrows > 0) why = "attribute stiffness / smoothness rows";
         if (!why && rs_on) why = "rolling shutter";
         if (!why && (central || opt.robust_loss)) why = "central differences / robust loss";
@@ -1968,6 +2125,9 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         trial_rec = trial_fold_ok && nranks == 1 && trial_records_ok(P) && maxpc <= 15 &&
                     sumpc == n_trial_other && nvar == ncf + sumpc &&
                     path_choice(MMBA_PATH_TRIAL_RECORDS) != 0;
+        // (a parameter that moves an object record: the trial's records come
+        // from the records launch, which rebuilds them)
+        if (obj_rec_moved) trial_rec = false;
         // without a solved bundle (C5): the same in k_trial_prep's place, when
         // every parameter outside the camera-frame blocks is a global that no
         // camera or bundle record reads (lens coefficients)

@@ -232,6 +232,16 @@ struct Plan {
     // some animated lens coefficient is hosted by one camera-frame and read
     // by others of its frame (Plan::build, mmba_lens_shared.hip)
     bool lens_shared = false;
+    // object records (mmba_object.hip; orec.n == 0: none): built with the
+    // camera and bundle records, read by k_jacobian / k_residual;
+    // obj_rec_moved: some parameter moves one (a record variant exists)
+    ObjRecDev orec;
+    bool obj_rec_moved = false;
+    // Unpinned choice of MMBA_PATH_OBJ_REC
+    static constexpr bool kObjRecDefault = true;
+    // where the build put each parameter (mmba_plan_param_layout): class and
+    // camera-frame / bundle index (-1 for a global)
+    std::vector<int> p_class_h, p_blk_h;
     double *d_ext_pertB = nullptr, *d_stepB = nullptr, *d_recsB = nullptr, *d_brecB = nullptr;
     std::vector<double> param_weight;  // paramWeightList (diag in mode 2)
     double *d_pweight = nullptr;       // ... on the device
@@ -679,6 +689,7 @@ int group_debug_damped_step(mmba_plan *plan, const double *x, double lam, double
 int group_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,
                        double *err_dist_out);
 int group_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out);
+const mmba_plan *group_first_plan(const mmba_plan *plan);  // mmba_plan_param_layout
 int group_plan_set_attr_values(mmba_plan *plan, const double *attr_values);
 int group_plan_solve_per_frame(mmba_plan *plan, double *x_inout, mmba_result *results,
                                const mmba_callbacks *cb);

@@ -469,6 +469,18 @@ class Solver:
         check(lib().mmba_plan_error_metrics(self._h, C.byref(st)))
         return {name: a[:F if name.startswith("frame") else K].copy() for name, a in mt.items()}
 
+    def param_layout(self):
+        """Where the plan put each parameter (``mmba_plan_param_layout``):
+        (class, block) int32 arrays -- class 0 camera-frame block, 1 bundle,
+        2 global; block the camera-frame index (frame-major numbering), the
+        bundle index, or -1."""
+        n = self.problem.num_params
+        cls, blk = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        check(lib().mmba_plan_param_layout(self._h, cls.ctypes.data_as(i32p),
+                                           blk.ctypes.data_as(i32p)))
+        return cls[:n], blk[:n]
+
     def set_attr_values(self, attr_values):
         """Replace the scene's attribute values of this plan
         (``mmba_plan_set_attr_values``; plan caching across solves)."""

@@ -894,6 +894,205 @@ def edge_scene(film_fit=abi.FILM_FIT_HORIZONTAL, render="narrow", film_offset=(0
     return prob
 
 
+def _trs(t, r, s=(1.0, 1.0, 1.0), roo=abi.ROO_XYZ):
+    """4 x 4 local matrices T R S of per-frame (or single) translate / rotate
+    (degrees) / scale, as mmba_geom.h trs_matrix forms them."""
+    t = np.atleast_2d(np.asarray(t, dtype=np.float64))
+    r = np.atleast_2d(np.asarray(r, dtype=np.float64))
+    M = np.zeros((t.shape[0], 4, 4))
+    M[:, :3, :3] = _euler(r[:, 0], r[:, 1], r[:, 2], roo) * np.asarray(s, dtype=np.float64)
+    M[:, :3, 3] = t
+    M[:, 3, 3] = 1.0
+    return M
+
+
+OBJECT_GROUP = dict(t=(0.3, -0.2, 0.5), r=(6.0, -9.0, 12.0), s=(1.2, 0.9, 1.1),
+                    roo=abi.ROO_YZX)
+
+
+def object_scene(frames=9, bundles=6, solve_bundles=False, solve_camera=False, window=0,
+                 objects=1, parent=False, cameras=1, seed=31) -> Problem:
+    """Object tracking: a rigid object keyed on every frame with ``bundles``
+    bundles parented under it, seen by one camera.
+
+    The camera moves as ``edge_scene``'s; its pose is fixed at the truth, or
+    (``solve_camera``) solved with frame 0 locked.  8 static scene bundles
+    stand behind the object, fixed, or with ``solve_camera`` solved (bundle 0
+    locked), so every frame has rows that no object parameter reaches.  Each
+    object's translate and rotate are animated and all six are solved at every
+    frame (6 F parameters per object, keyed ``param_frame >= 0``), starting
+    0.05 units / 1 degree off.  Its bundles' local positions lie in +-3; the
+    first three stay fixed at the truth (the gauge between object and
+    bundles), the others have their translate solved when ``solve_bundles``.
+    Markers are the pinhole projection of the truth plus noise.
+
+    ``window`` = w > 0: every bundle but each object's first three is seen on w
+    consecutive frames only, and on the last frame every object marker is
+    disabled (an object-frame no row reads).  ``parent``: the objects hang
+    under a static group that is translated, rotated and scaled, group and
+    objects with non-XYZ rotate orders; ``parent="solve"`` also solves the
+    group's rotation (three static parameters above the objects' bundles,
+    starting 0.5-1 degree off) and hangs four fixed bundles directly under the
+    group, which hold its pose.  ``cameras=2``: a second, fixed camera sees the
+    objects too (their parameters are then read by two cameras per frame)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    F, B = frames, bundles
+    b = SceneBuilder(F)
+    f = np.arange(F, dtype=np.float64)
+    # cameras: truth poses, the first as edge_scene's
+    cam_t = [np.stack([0.4 * f, 1.5 + 0.1 * f, -0.2 * f], axis=1)]
+    cam_r = [np.stack([2.0 + 0.5 * f, -8.0 + 0.7 * f, 1.0 + 0.3 * f], axis=1)]
+    if cameras > 1:
+        cam_t.append(np.stack([6.0 + 0.1 * f, 2.0 + 0.0 * f, 1.0 - 0.1 * f], axis=1))
+        cam_r.append(np.stack([1.0 + 0.0 * f, 6.0 + 0.2 * f, 0.0 * f], axis=1))
+    assert cameras in (1, 2)
+    t0 = cam_t[0] + rng.uniform(-0.05, 0.05, size=cam_t[0].shape)
+    r0 = cam_r[0] + rng.uniform(-1.0, 1.0, size=cam_r[0].shape)
+    if not solve_camera:
+        t0, r0 = cam_t[0].copy(), cam_r[0].copy()
+    t0[0], r0[0] = cam_t[0][0], cam_r[0][0]
+    cams, ctids = [], None
+    for c in range(cameras):
+        ct, cr = (t0, r0) if c == 0 else (cam_t[c], cam_r[c])
+        ctfm, tids = b.transform(t=[ct[:, 0], ct[:, 1], ct[:, 2]], r=[cr[:, 0], cr[:, 1], cr[:, 2]])
+        cam, _ = b.camera(ctfm, focal=FOCAL_MM, film_back=(FILM_W_IN, FILM_H_IN),
+                          render_size=RENDER)
+        cams.append(cam)
+        if c == 0:
+            ctids = tids
+    # the group above the objects
+    grp, gids, Mg = None, None, np.eye(4)[None]
+    oroo = abi.ROO_XYZ
+    if parent:
+        G = OBJECT_GROUP
+        g0 = G["r"]
+        if parent == "solve":
+            g0 = tuple(v + sgn * rng.uniform(0.5, 1.0) for v, sgn in zip(G["r"], (1, -1, 1)))
+        grp, gids = b.transform(t=G["t"], r=g0, s=G["s"], rotate_order=G["roo"])
+        Mg = _trs(G["t"], G["r"], G["s"], G["roo"])
+        oroo = abi.ROO_ZXY
+    # objects and their bundles
+    world, bnd_ids, otids_all, obj_of = [], [], [], []
+    for o in range(objects):
+        ot = np.stack([-2.0 + 4.0 * o + 0.3 * f, 1.5 + 0.1 * f - 0.5 * o, -25.0 - 0.2 * f - 3.0 * o],
+                      axis=1)
+        orot = np.stack([5.0 + 2.0 * f, -10.0 + 3.0 * f + 7.0 * o, 2.0 + 1.0 * f], axis=1)
+        ot0 = ot + rng.uniform(-0.05, 0.05, size=ot.shape)
+        or0 = orot + rng.uniform(-1.0, 1.0, size=orot.shape)
+        otfm, otids = b.transform(t=[ot0[:, 0], ot0[:, 1], ot0[:, 2]],
+                                  r=[or0[:, 0], or0[:, 1], or0[:, 2]], parent=grp,
+                                  rotate_order=oroo)
+        otids_all.append(otids)
+        L = rng.uniform(-3.0, 3.0, size=(B, 3))
+        L0 = L * (1.0 + rng.uniform(-0.03, 0.03, size=(B, 1)))
+        L0[:3] = L[:3]
+        if not solve_bundles:
+            L0 = L.copy()
+        Mw = Mg @ _trs(ot, orot, roo=oroo)  # (F, 4, 4)
+        for j in range(B):
+            bt, ids = b.transform(t=tuple(L0[j]), parent=otfm)
+            b.bundle(bt)
+            bnd_ids.append(ids)
+            obj_of.append(o)
+            world.append(Mw[:, :3, :3] @ L[j] + Mw[:, :3, 3])  # (F, 3)
+    # the group's rotation solved: four fixed bundles directly under the group
+    # hold its pose, which the objects' per-frame poses could otherwise absorb
+    if parent == "solve":
+        GL = np.stack([rng.uniform(-5.0, 5.0, 4), rng.uniform(-3.0, 3.0, 4),
+                       rng.uniform(-30.0, -20.0, 4)], axis=1)
+        for j in range(4):
+            bt, _ids = b.transform(t=tuple(GL[j]), parent=grp)
+            b.bundle(bt)
+            world.append(np.repeat((Mg[0, :3, :3] @ GL[j] + Mg[0, :3, 3])[None], F, 0))
+            obj_of.append(-2)
+    # scene bundles
+    depth = rng.uniform(30.0, 45.0, size=8)
+    S = np.stack([rng.uniform(-0.3, 0.3, 8) * depth, 1.5 + rng.uniform(-0.2, 0.2, 8) * depth,
+                  -depth], axis=1)
+    S0 = S * (1.0 + rng.uniform(-0.03, 0.03, size=(8, 1)))
+    S0[0] = S[0]
+    if not solve_camera:
+        S0 = S.copy()
+    scene_ids = []
+    for j in range(8):
+        bt, ids = b.transform(t=tuple(S0[j]))
+        b.bundle(bt)
+        scene_ids.append(ids)
+        world.append(np.repeat(S[j][None], F, 0))
+        obj_of.append(-1)
+    # markers: every camera sees the objects' bundles, the first the scene's too
+    for c in range(cameras):
+        R = _euler_xyz(cam_r[c][:, 0], cam_r[c][:, 1], cam_r[c][:, 2])
+        for j, X in enumerate(world):
+            if obj_of[j] < 0 and c > 0:
+                continue
+            pc = np.einsum("fij,fi->fj", R, X - cam_t[c])
+            mx = _noisy(rng, FOCAL_MM * pc[:, 0] / (FILM_W_MM * -pc[:, 2]))
+            my = _noisy(rng, FOCAL_MM * pc[:, 1] / (FILM_H_MM * -pc[:, 2]))
+            en = np.ones(F, dtype=bool)
+            if window > 0 and obj_of[j] >= 0:
+                if j % B >= 3:
+                    s0 = int(rng.integers(0, max(F - window, 0) + 1))
+                    en[:] = False
+                    en[s0:s0 + window] = True
+                en[F - 1] = False
+            b.marker(cams[c], j, np.stack([mx, my], axis=1), enable=en)
+    # parameters: camera, group, objects, object bundles, scene bundles
+    if solve_camera:
+        for a in ctids[:6]:
+            b.solve(a)
+    if parent == "solve":
+        for a in gids[3:6]:
+            b.solve(a)
+    for otids in otids_all:
+        for a in otids[:6]:
+            b.solve(a)
+    if solve_bundles:
+        for j, ids in enumerate(bnd_ids):
+            if j % B >= 3:
+                for a in ids[:3]:
+                    b.solve(a)
+    if solve_camera:
+        for ids in scene_ids[1:]:
+            for a in ids[:3]:
+                b.solve(a)
+    prob = b.build(meta={"name": "object", "object_attrs": [ids[:6] for ids in otids_all]})
+    if solve_camera:  # camera pose at frame 0 locked (parameters of frame 0 dropped)
+        keep = ~(np.isin(prob.param_attr, ctids[:6]) & (prob.param_frame == 0))
+        for name in ("param_attr", "param_frame", "param_min", "param_max", "param_offset",
+                     "param_scale", "x0"):
+            setattr(prob, name, np.ascontiguousarray(getattr(prob, name)[keep]))
+    return prob
+
+
+# The object scenes the tests solve against the oracle (tests/test_object_host.py,
+# tests/test_gpu_object.py); tools/object_envelope.py records the oracle's own
+# stability on each.
+OBJECT_TEST_SCENES = {
+    "above_cap": dict(frames=9, bundles=6),
+    "crosses_workgroup": dict(frames=10, bundles=6),
+    "solved_bundles": dict(frames=10, bundles=6, solve_bundles=True),
+    "solved_camera": dict(frames=9, bundles=6, solve_camera=True),
+    "windows": dict(frames=10, bundles=12, window=5),
+    "parent": dict(frames=9, bundles=6, parent=True, seed=34),
+    "parent_solved": dict(frames=9, bundles=6, parent="solve"),
+    "below_cap": dict(frames=6, bundles=6),
+}
+
+
+def object_options(scene_graph_mode=abi.SCENE_GRAPH_MODE_MAYA_DAG,
+                   solver_type=abi.SOLVER_TYPE_CMINPACK_LMDER, **kw):
+    """Options of the object scenes' solves.  lmdif counts its difference
+    evaluations (100 would end the solve inside the first Jacobian) and steps
+    by sqrt(delta) |x|: at the default 1e-4 that is 0.25 units on a translate
+    of 25, too coarse to converge on; 1e-8 steps by 1e-4 |x|."""
+    from .options import make_options
+    if solver_type == abi.SOLVER_TYPE_CMINPACK_LMDIF:
+        kw.setdefault("iterations", 1000)
+        kw.setdefault("delta", 1e-8)
+    return make_options(scene_graph_mode=scene_graph_mode, solver_type=solver_type, **kw)
+
+
 def rig_scene(n_cams=2, bundles=10, solve_cam1=True, stiffness=False, seed=11) -> Problem:
     """Static rig: ``n_cams`` cameras with static (non-animated) poses 1.5
     units apart on one frame, bundles in front solved (translate), camera 1's
