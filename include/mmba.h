@@ -806,7 +806,12 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                                      once per evaluation (plans on the generic Jacobian kernel:
                                      forward differences, no rolling shutter, one device).
                                      Default: 1 */
-#define MMBA_PATH_NUM 29
+#define MMBA_PATH_PCR_WIDE 29     /* 0: parallel cyclic reduction always launches its
+                                     256-thread workgroups; any other value: the 512-thread
+                                     form wherever its grid is resident (the default).  No
+                                     value forces the 512-thread form: beyond residency its
+                                     workgroups would wait on blocks that are not running */
+#define MMBA_PATH_NUM 30
 int mmba_debug_set_path(int key, int value);
 
 /* Test hook (not part of the solver seam): solve S x = r with the device
@@ -815,7 +820,10 @@ int mmba_debug_set_path(int key, int value);
  * rows are dense ("arrow").  P > 0 forces the number of band partitions
  * (nested dissection on the band rows), P <= 0 uses the solver's heuristic.
  * S is row-major, only its lower triangle is read.  ynorm2 = ||L^-1 r||^2 (the
- * quantity lmpar's Newton correction uses); parts_used = partitions run. */
+ * quantity lmpar's Newton correction uses); parts_used = partitions run, or
+ * -2 / -3 where parallel cyclic reduction ran in its 512- / 256-thread form
+ * (P = -1, no arrow, w <= 24, grid resident; P = -2: block cyclic reduction
+ * only). */
 int mmba_debug_band_solve(mmba_context *ctx, int nb, int w, int nG, int P, const double *S,
                           const double *r, double *x, double *ynorm2, int *parts_used);
 /* Test hook (not part of the solver seam): the in-place all-reduce a sharded

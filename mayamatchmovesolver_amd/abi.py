@@ -53,7 +53,8 @@ PATH_TRIAL_RED_FOLD = 25
 PATH_LENS_SHARED = 26
 PATH_OBJ_CF = 27
 PATH_OBJ_REC = 28
-PATH_NUM = 29
+PATH_PCR_WIDE = 29
+PATH_NUM = 30
 
 FILM_FIT_FILL = 0
 FILM_FIT_HORIZONTAL = 1

@@ -18,10 +18,10 @@ namespace mmba {
 static thread_local std::string g_last_error;
 void set_error(const std::string &msg) { g_last_error = msg; }
 
-static_assert(MMBA_PATH_NUM == 29, "one initialiser per path key");
+static_assert(MMBA_PATH_NUM == 30, "one initialiser per path key");
 static std::atomic<int> g_path[MMBA_PATH_NUM] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
                                                  -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                                                 -1, -1, -1, -1};
+                                                 -1, -1, -1, -1, -1};
 int path_choice(int key) {
     return (key > 0 && key < MMBA_PATH_NUM) ? g_path[key].load() : -1;
 }
@@ -683,7 +683,7 @@ int mmba_debug_band_solve(mmba_context *ctx, int nb, int w, int nG, int P, const
                 for (double v : hy) acc += v * v;
             *ynorm2 = acc;
         }
-        if (parts_used) *parts_used = p.bs.use_pcr ? -2 : p.bs.P;
+        if (parts_used) *parts_used = p.bs.use_pcr ? (p.bs.pcr.nth == 512 ? -2 : -3) : p.bs.P;
         if (fail) {
             set_error("band factorisation: non-positive pivot");
             return MMBA_ERR_INVALID;

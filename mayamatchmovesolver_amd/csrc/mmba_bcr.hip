@@ -502,7 +502,9 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
     __syncthreads();
     stamp(1);
     // B. triangular solves, lane = right-hand-side column: wave 0 U1 | V1,
-    // wave 1 U2 | V2, wave 2 Y1 | y1, wave 3 Y2 | y2 (C^-1 never formed)
+    // wave 1 U2 | V2, wave 2 Y1 | y1, wave 3 Y2 | y2 (C^-1 never formed);
+    // y rides in lane 63, beyond the widest arrow's columns (NGMAX < 64)
+    static_assert(NGMAX < 64, "lane 63 carries the fused forward solve");
     {
         const int w = wv & 1;  // which neighbour
         if (w == 0 ? h1 : h2) {
@@ -513,7 +515,7 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
                 }
             } else if (lane < nG) {
                 bcr_trsv_col<K, KS>(sD[w], sRs[w], &sGT[w][lane], GS);
-            } else if (lane == 32 && fwd) {
+            } else if (lane == 63 && fwd) {
                 bcr_trsv_col<K, KS>(sD[w], sRs[w], &sR[w][0], 1);
             }
         }

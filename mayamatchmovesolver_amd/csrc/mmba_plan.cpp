@@ -2306,7 +2306,13 @@ void Plan::setup_band(int Pforce) {
                 if (!pcr_off && nG == 0 && B.K <= 24 && pcr_grid(B.nblk) <= resident) {
                     PcrDev &Q = bs.pcr;
                     Q.K = B.K;
-                    Q.nth = pcr_grid(B.nblk) <= pcr_resident_wide(B.K) ? 512 : 256;
+                    // MMBA_PATH_PCR_WIDE = 0 pins the 256-thread form (no pin forces the
+                    // 512-thread form: beyond its residency workgroups would wait on
+                    // blocks that are not running)
+                    Q.nth = path_choice(MMBA_PATH_PCR_WIDE) != 0 &&
+                                    pcr_grid(B.nblk) <= pcr_resident_wide(B.K)
+                                ? 512
+                                : 256;
                     Q.nb = nb;
                     Q.w = w;
                     Q.nblk = B.nblk;
@@ -2455,7 +2461,10 @@ void Plan::setup_band(int Pforce) {
         PcrDev &Q = bs.ipcr;
         Q.K = std::max(8, (w + 7) / 8 * 8);
         // (one process's PCR launches on a device are ordered, pcr_ordered)
-        Q.nth = pcr_grid((hp.r1 - hp.r0 + Q.K - 1) / Q.K) <= pcr_resident_wide(Q.K) ? 512 : 256;
+        Q.nth = path_choice(MMBA_PATH_PCR_WIDE) != 0 &&
+                        pcr_grid((hp.r1 - hp.r0 + Q.K - 1) / Q.K) <= pcr_resident_wide(Q.K)
+                    ? 512
+                    : 256;
         Q.nb = ast;
         Q.w = w;
         Q.nblk = (ast + Q.K - 1) / Q.K;

@@ -568,7 +568,10 @@ def set_path(key: int, value: int = -1) -> None:
 
 def debug_band_solve(ctx: "Context", S: np.ndarray, nb: int, w: int, nG: int, parts: int = 0):
     """Test hook: solve S x = r-style systems with the device band + arrow
-    Cholesky (``mmba_debug_band_solve``).  Returns a function r -> (x, ||L^-1 r||^2, P)."""
+    Cholesky (``mmba_debug_band_solve``).  Returns a function r -> (x, ||L^-1 r||^2, P);
+    P is the number of partitions run, or -2 / -3 where parallel cyclic
+    reduction ran in its 512- / 256-thread form (``abi.PATH_PCR_WIDE`` = 0 pins
+    the latter)."""
     S = np.ascontiguousarray(S, dtype=np.float64)
 
     def solve(r):

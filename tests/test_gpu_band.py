@@ -1,11 +1,17 @@
 """Device band + arrow Cholesky (csrc/mmba_band.hip) against numpy on random
 symmetric positive-definite matrices of the reduced-system shape: nb band rows
 of half bandwidth w plus nG dense arrow rows, with and without the partitioned
-(nested-dissection) path and with block cyclic reduction (P = -1).  Tolerance: fp64 direct solve, 1e-10 relative to
-max |x| on well-conditioned matrices."""
+(nested-dissection) path and with the log-depth solvers (P = -1: parallel
+cyclic reduction without an arrow at w <= 24, block cyclic reduction otherwise;
+P = -2: block cyclic reduction only), arrows up to NGMAX = 48.  Tolerance:
+fp64 direct solve, 1e-10 relative to max |x| on well-conditioned matrices.
+These matrices are diagonally dominant, so a block does not see the blocks
+beyond a few strides: tests/test_gpu_band_coupled.py holds the same solvers
+to systems on which every elimination level matters."""
 import numpy as np
 import pytest
 
+from mayamatchmovesolver_amd import abi
 from mayamatchmovesolver_amd.solver import debug_band_solve
 
 pytestmark = pytest.mark.gpu
@@ -47,10 +53,13 @@ CASES = [
     (1000, 32, 16, -1), (10, 2, 16, -1), (0, 0, 4, -1), (90, 5, 0, -1),
     (7, 3, 0, -1), (777, 31, 1, -1), (1000, 16, 3, -1), (17, 8, 2, -1),
     (2880, 11, 2, -1), (840, 6, 0, -1), (4096, 24, 0, -1), (24 * 65, 24, 1, -1),
-    # arrows wider than 16 (up to NGMAX = 32): band, partitioned, BCR K = 8..32
+    # arrows wider than 16 (up to NGMAX = 48; the partitioned chain carries 32,
+    # a wider arrow factors the band as one partition): band, partitioned, BCR
+    # K = 8..32
     (1000, 23, 24, 1), (1000, 40, 32, 4), (640, 60, 32, 1), (10, 2, 32, 1), (0, 0, 32, 1),
     (1000, 23, 24, -1), (1000, 32, 32, -1), (300, 6, 32, -1), (500, 16, 17, -1),
     (24 * 65, 24, 24, -1), (0, 0, 24, -1),
+    (640, 60, 48, 1), (1000, 40, 48, 1), (0, 0, 48, 1), (300, 6, 48, -1), (1000, 23, 40, -1),
 ]
 
 
@@ -67,6 +76,12 @@ def test_band_solve_matches_numpy(nb, w, nG, P, gpu_ctx):
     assert abs(yn - ynr) <= 1e-10 * abs(ynr)
     if P > 1:
         assert used > 1
+    # the solver that ran (parts_used: -2 / -3 = parallel cyclic reduction in
+    # its 512- / 256-thread form)
+    if P == -1 and nG == 0 and w <= 24:
+        assert used in (-2, -3)
+    if P == -2:
+        assert used not in (-2, -3)
 
 
 @pytest.mark.parametrize("M,N,K", [(300, 300, 64), (129, 129, 512), (1000, 1000, 256),
@@ -110,10 +125,20 @@ def test_dgemm_nt_in_place_panel(M, gpu_ctx):
     assert np.all(np.abs(got - A @ Li.T) <= 1e-13 * scale)
 
 
-@pytest.mark.parametrize("parts", [-1, -2])
-@pytest.mark.parametrize("nb,w,nG", [(2994, 23, 0), (500, 23, 3), (1000, 15, 0)])
-@pytest.mark.parametrize("where", ["odd_block", "even_block", "root", "arrow", "nan"])
-def test_bcr_indefinite_is_reported(nb, w, nG, where, parts, gpu_ctx):
+# every solver under its default pivot chain, and parallel cyclic reduction
+# (parts = -1 without an arrow) under the two alternative chains as well
+INDEFINITE = [pytest.param(nb, w, nG, where, parts, 0,
+                           id="%s-%d-%d-%d-%d" % (where, nb, w, nG, parts))
+              for parts in (-1, -2) for nb, w, nG in [(2994, 23, 0), (500, 23, 3), (1000, 15, 0)]
+              for where in ["odd_block", "even_block", "root", "arrow", "nan"]]
+INDEFINITE += [pytest.param(nb, w, 0, where, -1, chain,
+                            id="%s-%d-%d-0--1-chain%d" % (where, nb, w, chain))
+               for nb, w in [(2994, 23), (1000, 15)] for chain in (1, 2)
+               for where in ["odd_block", "even_block", "root", "nan"]]
+
+
+@pytest.mark.parametrize("nb,w,nG,where,parts,chain", INDEFINITE)
+def test_bcr_indefinite_is_reported(nb, w, nG, where, parts, chain, gpu_ctx, paths):
     """A non-positive (or NaN) pivot anywhere in the block cyclic reduction --
     a block eliminated at level 0, a block eliminated at a later level, the
     root block, the arrow corner -- is reported as a failed factorisation (the
@@ -129,6 +154,8 @@ def test_bcr_indefinite_is_reported(nb, w, nG, where, parts, gpu_ctx):
     row = {"odd_block": K + 3, "even_block": 2 * K + 5, "root": 2, "arrow": nb + nG - 1,
            "nan": 4 * K + 1}[where]
     S[row, row] = np.nan if where == "nan" else -10.0 * abs(S[row, row])
+    if chain:
+        paths(abi.PATH_PCR_CHAIN, chain)
     solve = debug_band_solve(gpu_ctx, S, nb, w, nG, parts=parts)
     with pytest.raises(MmbaError, match="non-positive pivot"):
         solve(np.ones(nb + nG))
