@@ -969,6 +969,18 @@ void Plan::newton_enqueue(double dxnorm) {
         launch_newton_bundle(s, schur_problem(), d_W, d_Wg, d_Lb, d_v, d_wR, d_usq, d_nu, d_ngp);
         launch_reduce_sum(s, d_usq, nB, d_scalar + SL_NEWT_B);
     }
+    // sharded with S all-reduced whole (the log-depth solvers on bs.red, the
+    // dense solver): every shard holds the whole factor and rank 0 counts the
+    // whole y = L^-1 w (d_ymask), so w must be whole too.  Each shard's own
+    // camera-frame rows are complete (its halo rows are partial: dropped) and
+    // the global rows are each shard's own bundles' terms: summed.  Without
+    // it lmpar's parl / parc (oracle/refcpu.c lmpar, MINPACK lmpar.f: the
+    // Newton correction ||R^-T D^2 x / dxnorm||) came from rank 0's rows alone
+    // whenever the Gauss-Newton step left the trust region.
+    if (nranks > 1 && nR > 0 && (bs.red || shard_dense)) {
+        launch_keep_rows(s, d_wR, Ra, Rb, nR - nG, nR, 1);
+        allreduce(d_wR, nRpad);
+    }
     if (nR > 0) {
         const Reduced kind = reduced_now();
         switch (kind) {

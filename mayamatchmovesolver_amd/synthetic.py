@@ -1428,6 +1428,98 @@ def witness_scene(n_witness=4, frames=6, bundles=24, solve_bundles=True, n_focal
     return b.build(meta={"name": "witness"})
 
 
+BOUND_KINDS = ("unbounded", "lower", "upper", "both")
+
+
+def bound_kinds(prob: Problem) -> np.ndarray:
+    """Index into BOUND_KINDS per parameter, read off param_min / param_max as
+    the reference reads them (a side is a bound when it is inside +-FLT_MAX)."""
+    lo = prob.param_min > -FLOAT_MAX
+    hi = prob.param_max < FLOAT_MAX
+    return (lo & ~hi) * 1 + (~lo & hi) * 2 + (lo & hi) * 3
+
+
+def param_classes(prob: Problem) -> np.ndarray:
+    """Host-side parameter class per parameter, by what the parameter is keyed
+    on: "bundle" (a bundle transform's translate), "object" (a pose attribute
+    of an object_scene object, keyed per frame), "lens" (a lens attribute
+    keyed per frame), "camera" (any other parameter keyed per frame) and
+    "global" (any other static parameter)."""
+    bnd_attrs = set()
+    for t in np.asarray(prob.bnd_tfm):
+        bnd_attrs.update(int(a) for a in prob.tfm_attrs[9 * t:9 * t + 3])
+    lens_attrs = set(int(a) for a in np.asarray(prob.lens_attrs) if a >= 0)
+    obj_attrs = set(int(a) for ids in prob.meta.get("object_attrs", []) for a in ids)
+    out = []
+    for a, f in zip(prob.param_attr.tolist(), prob.param_frame.tolist()):
+        if a in bnd_attrs:
+            out.append("bundle")
+        elif f < 0:
+            out.append("global")
+        elif a in obj_attrs:
+            out.append("object")
+        elif a in lens_attrs:
+            out.append("lens")
+        else:
+            out.append("camera")
+    return np.array(out)
+
+
+def with_bounds(prob: Problem, seed=0, weights=(0.3, 0.1, 0.3, 0.3), p_scale=0.3,
+                p_offset=0.3, keep=None) -> Problem:
+    """TEST HELPER (no product path calls it): the bounded twin of a built
+    problem.  Every parameter gets one of BOUND_KINDS from a generator seeded
+    with ``seed`` (``weights``: their probabilities):
+      unbounded;
+      lower only, lo = the current external value -- the reference's
+        lower-only transform always returns xmin (Appendix B2), so the
+        parameter stays frozen where it is (a bound below the value would
+        move it there and wreck the scene);
+      upper only, hi = value + U(0.5, 3);
+      both, [value - U(0.5, 3), value + U(0.5, 3)].
+    About ``p_scale`` of the parameters get scale 2 and about ``p_offset``
+    offset 0.5.  Within each class of ``param_classes`` that has at least four
+    parameters the first four of a seeded shuffle take the four kinds, and the
+    next two scale 2 and offset 0.5 on a bounded kind, so every class holds
+    every kind whatever the draw.  ``keep``: boolean mask of parameters left
+    as they are.  x0 is recomputed with param_external_to_internal."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = prob.num_params
+    kind = rng.choice(4, size=n, p=np.asarray(weights, dtype=np.float64))
+    du, dl = rng.uniform(0.5, 3.0, size=n), rng.uniform(0.5, 3.0, size=n)
+    scaled, shifted = rng.random(n) < p_scale, rng.random(n) < p_offset
+    touch = np.ones(n, bool) if keep is None else ~np.asarray(keep, bool)
+    cls = param_classes(prob)
+    for c in sorted(set(cls[touch].tolist())):
+        idx = rng.permutation(np.flatnonzero((cls == c) & touch))
+        if idx.size >= 4:
+            kind[idx[:4]] = np.arange(4)
+            scaled[idx[2]], shifted[idx[3]] = True, True
+    ext0 = prob.external_params(prob.x0)
+    d = prob.to_npz_dict()
+    lo, hi = d["param_min"].copy(), d["param_max"].copy()
+    off, scl, x0 = d["param_offset"].copy(), d["param_scale"].copy(), d["x0"].copy()
+    for p in np.flatnonzero(touch):
+        lo[p] = ext0[p] if kind[p] == 1 else ext0[p] - dl[p] if kind[p] == 3 else -FLOAT_MAX
+        hi[p] = ext0[p] + du[p] if kind[p] >= 2 else FLOAT_MAX
+        scl[p] = 2.0 if scaled[p] else 1.0
+        off[p] = 0.5 if shifted[p] else 0.0
+        x0[p] = param_external_to_internal(float(ext0[p]), float(lo[p]), float(hi[p]),
+                                           float(off[p]), float(scl[p]))
+    d.update(param_min=lo, param_max=hi, param_offset=off, param_scale=scl, x0=x0)
+    twin = Problem.from_npz_dict(d)
+    twin.meta = dict(prob.meta)
+    return twin
+
+
+def flipped_columns(prob: Problem, delta: float, x=None) -> np.ndarray:
+    """The parameters whose lmder difference step is negative at x (default
+    x0): the internal value + delta is above the external upper bound and the
+    value - delta not below the lower one (adjust_solveFunc.cpp:148-180)."""
+    v = prob.x0 if x is None else np.asarray(x, dtype=np.float64)
+    return ((v + delta) > prob.param_max) & ~((v - delta) < prob.param_min)
+
+
 def config_options(prob: Problem, scene_graph_mode=abi.SCENE_GRAPH_MODE_MM_SCENE_GRAPH,
                    **overrides):
     """Solver options for a synthetic config (lmder, forward FD,
