@@ -32,25 +32,9 @@
 #include <cstdlib>
 
 #include "mmba_kernels.h"
+#include "mmba_wave_dev.h"
 
 namespace mmba {
-
-// Broadcast lane l's double to the whole wave (v_readlane: l is wave-uniform).
-__device__ __forceinline__ double rdlane(double v, int l) {
-    const long long x = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(x & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(x >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// 1/sqrt(d): v_rsq_f64 plus two Newton steps (full fp64 precision).
-__device__ __forceinline__ double rsq_nr(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-    const double h = 0.5 * d;
-    y = y * fma(-h * y, y, 1.5);
-    y = y * fma(-h * y, y, 1.5);
-    return y;
-}
 
 // Row q of a packed lower triangle holding entry e (q(q+1)/2 <= e).
 __device__ __forceinline__ int tri_row(int e) {
@@ -73,23 +57,23 @@ __device__ __forceinline__ int potrf_inv(double (&a)[NB], double (&x)[NB]) {
     double y[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-        double d = rdlane(a[j], j);
+        double d = wave_rdlane(a[j], j);
         if (!(d > 0.) || !isfinite(d)) {
             badl = 1;
             d = 1.;
             if (r == j) a[j] = 1.;
         }
-        y[j] = rsq_nr(d);
+        y[j] = wave_rsq(d);
         const double lj = a[j] * y[j];  // lane j: sqrt(d); lanes > j: L[r][j]
         a[j] = lj;
 #pragma unroll
-        for (int c = j + 1; c < NB; ++c) a[c] = fma(-lj, rdlane(lj, c), a[c]);
+        for (int c = j + 1; c < NB; ++c) a[c] = fma(-lj, wave_rdlane(lj, c), a[c]);
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
         double s = (i == r) ? 1. : 0.;
 #pragma unroll
-        for (int t = 0; t < i; ++t) s = fma(-rdlane(a[t], i), x[t], s);
+        for (int t = 0; t < i; ++t) s = fma(-wave_rdlane(a[t], i), x[t], s);
         x[i] = s * y[i];
     }
     return badl;
@@ -303,7 +287,7 @@ __global__ void __launch_bounds__(256)
         for (int k = 0; k < 4; ++k) atomicAdd((unsigned long long *)&probe[k], (unsigned long long)pt[k]);
 }
 
-// Sum over the 16 lanes of a lane group.
+// Sum over the 16 lanes of a lane group (not wave_sum: 16 wide).
 __device__ __forceinline__ double sum16(double v) {
     v += __shfl_xor(v, 8, 16);
     v += __shfl_xor(v, 4, 16);
@@ -644,7 +628,6 @@ __global__ void k_sep_back(const BandPart *__restrict__ part, const double *__re
 // ---------------------------------------------------------------------------
 // Host side.
 // ---------------------------------------------------------------------------
-static inline int nblk_(long n, int bs) { return (int)((n + bs - 1) / bs); }
 
 void band_factor(hipStream_t s, const BandSolver &B, int *fail, long long *probe) {
     if (B.use_bcr) {
@@ -663,7 +646,7 @@ void band_factor(hipStream_t s, const BandSolver &B, int *fail, long long *probe
     const int nbT = (B.P - 1) * B.w;
     const int nloc = B.p_hi - B.p_lo;
     {
-        dim3 grid(nblk_(B.max_arrow, 256), nloc);
+        dim3 grid(nblk(B.max_arrow, 256), nloc);
         k_band_extract<<<grid, 256, 0, s>>>(B.Bd, B.w, B.Ga, B.nb, B.d_parts + B.p_lo, nloc,
                                             B.apool);
     }
@@ -673,7 +656,7 @@ void band_factor(hipStream_t s, const BandSolver &B, int *fail, long long *probe
         const int ast = hp.r1 - hp.r0;
         pcr_solve(s, B.ipcr, B.izero, B.ix, nullptr, fail);
         pcr_rhs_mc(s, B.ipcr, B.apool + hp.aoff, ast, hp.na, B.XA, ast, fail);
-        k_sep_z<<<nblk_((long)hp.na * (hp.na + 1) / 2, 256), 256, 0, s>>>(
+        k_sep_z<<<nblk((long)hp.na * (hp.na + 1) / 2, 256), 256, 0, s>>>(
             B.d_parts + B.p_lo, B.w, B.apool, B.XA, B.zpool);
     } else {
         k_band_factor<8, 64, WBAND_PART, 2 * WBAND_PART + NGPART, false><<<nloc, 256, 0, s>>>(
@@ -681,7 +664,7 @@ void band_factor(hipStream_t s, const BandSolver &B, int *fail, long long *probe
     }
     {
         const int n = nbT * (2 * B.w) + B.nG * nbT + NGMAX * NGMAX;
-        k_band_tassemble<<<nblk_(n, 256), 256, 0, s>>>(B.Bd, B.w, B.Ga, B.Gd, B.nb, B.nG,
+        k_band_tassemble<<<nblk(n, 256), 256, 0, s>>>(B.Bd, B.w, B.Ga, B.Gd, B.nb, B.nG,
                                                        B.d_parts, B.P, B.p_lo, B.p_hi, B.zpool,
                                                        B.TBd, B.TGa, B.TGd);
     }
@@ -725,12 +708,12 @@ void band_forward(hipStream_t s, const BandSolver &B, const double *r, double *y
         k_band_fwd<8, 64, false><<<nloc, 256, 0, s>>>(B.Bd, B.w, B.nb, B.d_parts + B.p_lo,
                                                        B.apool, B.Dinv, nullptr, B.cpool, r, y);
     }
-    k_band_trhs<<<nblk_(nbT + B.nG, 256), 256, 0, s>>>(r, B.w, B.nb, B.nG, B.d_parts, B.P,
+    k_band_trhs<<<nblk(nbT + B.nG, 256), 256, 0, s>>>(r, B.w, B.nb, B.nG, B.d_parts, B.P,
                                                        B.p_lo, B.p_hi, B.cpool, B.rT);
     if (B.comm) B.comm->allreduce(B.rT, nbT + B.nG, ReduceOp::Sum, s);
     k_band_fwd<8, 128, true><<<1, 256, 0, s>>>(B.TBd, 2 * B.w - 1, nbT, B.d_tpart, B.TGa,
                                                 B.TDinv, B.TGdinv, nullptr, B.rT, B.yT);
-    k_band_tscatter<<<nblk_(nbT + B.nG, 256), 256, 0, s>>>(B.yT, B.w, B.nb, B.nG, B.d_parts,
+    k_band_tscatter<<<nblk(nbT + B.nG, 256), 256, 0, s>>>(B.yT, B.w, B.nb, B.nG, B.d_parts,
                                                            B.P, y);
 }
 
@@ -753,11 +736,11 @@ void band_backward(hipStream_t s, const BandSolver &B, const double *y, double *
     // left for this y), then every partition
     k_band_bwd<8, 128, true><<<1, 256, 0, s>>>(B.TBd, 2 * B.w - 1, nbT, B.d_tpart, B.TGa,
                                                 B.TDinv, B.TGdinv, B.yT, B.xT);
-    k_band_tscatter<<<nblk_(nbT + B.nG, 256), 256, 0, s>>>(B.xT, B.w, B.nb, B.nG, B.d_parts,
+    k_band_tscatter<<<nblk(nbT + B.nG, 256), 256, 0, s>>>(B.xT, B.w, B.nb, B.nG, B.d_parts,
                                                            B.P, x);
     if (B.pcr_int && !B.df_off) {  // (a timed-out wait: the band chains)
         const int ast = B.hpart.r1 - B.hpart.r0;
-        k_sep_back<<<nblk_(ast, 256), 256, 0, s>>>(B.d_parts + B.p_lo, B.XA, y, x);
+        k_sep_back<<<nblk(ast, 256), 256, 0, s>>>(B.d_parts + B.p_lo, B.XA, y, x);
         return;
     }
     k_band_bwd<8, 64, false><<<B.p_hi - B.p_lo, 256, 0, s>>>(

@@ -27,6 +27,7 @@
 #include "mmba_geom.h"
 #include "mmba_kernels.h"
 #include "mmba_plan.h"
+#include "mmba_wave_dev.h"
 
 namespace mmba {
 
@@ -34,39 +35,9 @@ namespace {
 
 constexpr int BT = 256;  // threads per frame workgroup
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return wave_rdlane(v, 0);
-}
-
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return wave_rdlane(v, 0);
-}
-
-// Augmented Cholesky of one wave (mmba_bdiag.hip bd_chol_aug with NF rows):
-// lane i < NF holds row i, lane NF the right-hand side; afterwards rows
-// hold C (diagonal sqrt(d), rsl = 1/sqrt(d)) and lane NF holds C^-1 b.
-template <int NF>
-__device__ __forceinline__ void chol_aug(double (&a)[NF], double &rsl, bool &bad) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int j = 0; j < NF; ++j) {
-        double d = wave_rdlane(a[j], j);
-        if (!(d > 0.) || !isfinite(d)) {
-            bad = true;
-            d = 1.;
-        }
-        const double rs = wave_rsq(d);
-        const double l = (lane > j) ? a[j] * rs : 0.;
-        a[j] = (lane == j) ? d * rs : (lane > j ? l : a[j]);
-        if (lane == j) rsl = rs;
-#pragma unroll
-        for (int c = j + 1; c < NF; ++c) a[c] = fma(-l, wave_rdlane(l, c), a[c]);
-    }
-}
+// wave sum / maximum as a wave-uniform (scalar) value
+__device__ __forceinline__ double wsum(double v) { return wave_rdlane(wave_sum(v), 0); }
+__device__ __forceinline__ double wmax(double v) { return wave_rdlane(wave_max(v), 0); }
 
 struct EvalR {
     double fsq, jp, dsum, dmin, dmax;
@@ -424,7 +395,7 @@ __global__ void __launch_bounds__(BT) k_batch_lm(DevProblem P, BatchArgs B) {
                             a[c] = v;
                         }
                         bool bad = false;
-                        chol_aug<NF>(a, rsl, bad);
+                        wave_chol_aug<NF>(a, rsl, bad);
                         // x = C^-T y, y = C^-1 b in lane NF
                         double acc = 0.;
 #pragma unroll

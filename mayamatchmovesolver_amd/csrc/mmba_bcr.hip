@@ -52,9 +52,9 @@ __device__ __forceinline__ double *bcr_blk(double *base, int b, int K) {
 __device__ __forceinline__ double bcr_get(const double *v, int R, int nb) {
     return R < nb ? v[R] : 0.;
 }
-// bcr_get of a handed-off vector (sc1 load, see bcr_ld)
+// bcr_get of a handed-off vector (sc1 load, see ld_sc1)
 __device__ __forceinline__ double bcr_get_sc1(const double *v, int R, int nb) {
-    return R < nb ? bcr_ld(v + R) : 0.;
+    return R < nb ? ld_sc1(v + R) : 0.;
 }
 
 
@@ -106,6 +106,8 @@ __device__ __forceinline__ void bcr_chol_inv_wave(double *M, double *Ci, double 
     for (int c = 0; c < K; ++c) a[c] = (lane < K && c <= lane) ? M[lane * KS + c] : 0.;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
+        // wave_rdlane written out: the call changes the register allocation of
+        // k_bcr_factor_df
         const long long dv = __double_as_longlong(a[j]);
         const int lo = __builtin_amdgcn_readlane((int)(dv & 0xffffffffll), j);
         const int hi = __builtin_amdgcn_readlane((int)(dv >> 32), j);
@@ -114,7 +116,7 @@ __device__ __forceinline__ void bcr_chol_inv_wave(double *M, double *Ci, double 
             bad = 1;
             d = 1.;
         }
-        const double rs = bcr_rsq(d);
+        const double rs = wave_rsq(d);
         rsv[j] = rs;  // wave-uniform: 1 / C_jj
         const double l = (lane > j) ? a[j] * rs : 0.;
         a[j] = (lane == j) ? d * rs : (lane > j ? l : a[j]);
@@ -162,10 +164,10 @@ __device__ __forceinline__ void bcr_chol_wave(double *M, double *rs_out, double 
     // formed before the LDS round trip of the remaining columns -- the
     // pivot chain overlaps the bulk update.  Same operations and operands as
     // the plain loop (a[j+1] = fma(-l, col[j+1], a[j+1]) with col[j+1] = l_(j+1)).
-    double d = bcr_rdlane(a[0], 0);
+    double d = wave_rdlane(a[0], 0);
     bool dbad = !(d > 0.) || !isfinite(d);
     if (dbad) d = 1.;
-    double rs = bcr_rsq(d);
+    double rs = wave_rsq(d);
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         if (dbad) bad = 1;
@@ -174,12 +176,12 @@ __device__ __forceinline__ void bcr_chol_wave(double *M, double *rs_out, double 
         if (lane < K) col[lane] = l;
         if (lane == 0) rs_out[j] = rs;
         if (j + 1 < K) {
-            const double lj1 = bcr_rdlane(l, j + 1);
+            const double lj1 = wave_rdlane(l, j + 1);
             a[j + 1] = fma(-l, lj1, a[j + 1]);
-            d = bcr_rdlane(a[j + 1], j + 1);
+            d = wave_rdlane(a[j + 1], j + 1);
             dbad = !(d > 0.) || !isfinite(d);
             if (dbad) d = 1.;
-            rs = bcr_rsq(d);
+            rs = wave_rsq(d);
         }
         wave_lds_sync();
 #pragma unroll
@@ -205,8 +207,8 @@ __device__ __forceinline__ void bcr_chol_aug_wave(double (&a)[K], double *rs_out
     // per-step bookkeeping stays in one register each: lane j keeps 1 / C_jj
     // (stored once after the chain), the pivot checks fold into one flag
     double rsl = 0.;
-    double d = bcr_rdlane(a[0], 0);
-    double rs = bcr_rsq(d);  // bad pivots: checked once after the chain (bcr_chol_aug_blk)
+    double d = wave_rdlane(a[0], 0);
+    double rs = wave_rsq(d);  // bad pivots: checked once after the chain (bcr_chol_aug_blk)
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         const double l = (lane > j) ? a[j] * rs : 0.;
@@ -220,10 +222,10 @@ __device__ __forceinline__ void bcr_chol_aug_wave(double (&a)[K], double *rs_out
 #pragma unroll
         for (int c = j + 2; c < K; ++c) cv[c] = col[c];
         if (j + 1 < K) {
-            const double lj1 = bcr_rdlane(l, j + 1);
+            const double lj1 = wave_rdlane(l, j + 1);
             a[j + 1] = fma(-l, lj1, a[j + 1]);
-            d = bcr_rdlane(a[j + 1], j + 1);
-            rs = bcr_rsq(d);
+            d = wave_rdlane(a[j + 1], j + 1);
+            rs = wave_rsq(d);
         }
 #pragma unroll
         for (int c = j + 2; c < K; ++c) a[c] = fma(-l, cv[c], a[c]);
@@ -291,8 +293,8 @@ __device__ __forceinline__ void bcr_updates_mfma(const double *U1, const double 
     for (int r = 0; r < 4; ++r) {
         const int row = ti * 16 + k4 + 4 * r, col = tc * 16 + (lane & 15);
         if (row < K && col < K) {
-            if (dtile && col <= row) bcr_st(&De[row * K + col], sDe[row * KS + col] - dacc[r]);
-            if (h1) bcr_st(&Lo[row * K + col], -lacc[r]);
+            if (dtile && col <= row) st_sc1(&De[row * K + col], sDe[row * KS + col] - dacc[r]);
+            if (h1) st_sc1(&Lo[row * K + col], -lacc[r]);
         }
     }
 }
@@ -390,13 +392,13 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
         } else {
             // lower part only (the upper part of a stored block is never written)
             // (stored by the previous level's items of this launch: sc1 loads)
-            if (h1 && c <= i) d0 = bcr_ld(bcr_blk(B.Dk, o1, K) + q);
-            if (h2 && c <= i) d1 = bcr_ld(bcr_blk(B.Dk, o2, K) + q);
-            if (h1) b0 = bcr_ld(bcr_blk((double *)Lin, o1, K) + q);
-            if (h1) b1 = bcr_ld(bcr_blk((double *)Lin, e, K) + q);
-            if (h2) b2 = bcr_ld(bcr_blk((double *)Lin, o2, K) + q);
-            if (hn) b3 = bcr_ld(bcr_blk((double *)Lin, en, K) + q);
-            de = bcr_ld(bcr_blk(B.Dk, e, K) + q);
+            if (h1 && c <= i) d0 = ld_sc1(bcr_blk(B.Dk, o1, K) + q);
+            if (h2 && c <= i) d1 = ld_sc1(bcr_blk(B.Dk, o2, K) + q);
+            if (h1) b0 = ld_sc1(bcr_blk((double *)Lin, o1, K) + q);
+            if (h1) b1 = ld_sc1(bcr_blk((double *)Lin, e, K) + q);
+            if (h2) b2 = ld_sc1(bcr_blk((double *)Lin, o2, K) + q);
+            if (hn) b3 = ld_sc1(bcr_blk((double *)Lin, en, K) + q);
+            de = ld_sc1(bcr_blk(B.Dk, e, K) + q);
         }
         sD[0][x] = d0;
         sD[1][x] = d1;
@@ -414,14 +416,14 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
         if (h && qq < nG) {
             const int C = o * K + u;
             g = band ? (C < B.nb ? B.Ga[(size_t)qq * B.nb + C] : 0.)
-                     : bcr_ld(&B.Gk[((size_t)o * nG + qq) * K + u]);
+                     : ld_sc1(&B.Gk[((size_t)o * nG + qq) * K + u]);
         }
         sGT[which][r] = g;
     }
     for (int q = tid; q < nG * K; q += blockDim.x) {
         const int C = e * K + q % K;
         sGe[q] = band ? (C < B.nb ? B.Ga[(size_t)(q / K) * B.nb + C] : 0.)
-                      : bcr_ld(&B.Gk[(size_t)e * nG * K + q]);
+                      : ld_sc1(&B.Gk[(size_t)e * nG * K + q]);
     }
     if (tid < 3 * K) sR[tid / K][tid % K] = rv;
     __syncthreads();
@@ -549,7 +551,7 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
             }
 #pragma unroll
             for (int c = 0; c < CG; ++c)
-                if (c0 + c <= i) bcr_st(&De[i * K + c0 + c], sDe[i * KS + c0 + c] - acc[c]);
+                if (c0 + c <= i) st_sc1(&De[i * K + c0 + c], sDe[i * KS + c0 + c] - acc[c]);
         } else if (h1) {
             double acc[CG];
 #pragma unroll
@@ -561,7 +563,7 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
                 for (int c = 0; c < CG; ++c) acc[c] = fma(v, U1[u * KS + c0 + c], acc[c]);
             }
 #pragma unroll
-            for (int c = 0; c < CG; ++c) bcr_st(&bcr_blk(Lout, e, K)[i * K + c0 + c], -acc[c]);
+            for (int c = 0; c < CG; ++c) st_sc1(&bcr_blk(Lout, e, K)[i * K + c0 + c], -acc[c]);
         }
     }
     if (fwd) {  // r_e -= V1^T y1 + U2^T y2; the owner of o2 stores y2 and Y2^T y2
@@ -574,7 +576,7 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
                 acc1 = fma(U2[u * KS + ft], sR[1][u], acc1);
             }
             const int R = e * K + ft;
-            if (R < B.nb) bcr_st(&B.rw[R], sR[2][ft] - (acc0 + acc1));
+            if (R < B.nb) st_sc1(&B.rw[R], sR[2][ft] - (acc0 + acc1));
         } else if (h2 && ft >= 32 && ft < 32 + K) {
             const int i = ft - 32, R = o2 * K + i;
             if (R < B.nb) y[R] = sR[1][i];
@@ -582,7 +584,7 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
             const int q = ft - 64;
             double acc = 0.;
             for (int u = 0; u < K; ++u) acc = fma(Y2[u * GS + q], sR[1][u], acc);
-            bcr_st(&B.gpart[(size_t)o2 * nG + q], acc);
+            st_sc1(&B.gpart[(size_t)o2 * nG + q], acc);
         }
     }
     if (pub && nG == 0) {
@@ -592,7 +594,7 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0)
-            __hip_atomic_store((bcr_gu32 *)pub, pub_epoch, __ATOMIC_RELAXED,
+            __hip_atomic_store((gu32_t *)pub, pub_epoch, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
     }
     for (int q = tid; q < nG * 4; q += blockDim.x) {
@@ -609,7 +611,7 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
         }
 #pragma unroll
         for (int c = 0; c < CG; ++c)
-            bcr_st(&B.Gk[((size_t)e * nG + qq) * K + c0 + c], sGe[qq * K + c0 + c] - acc[c]);
+            st_sc1(&B.Gk[((size_t)e * nG + qq) * K + c0 + c], sGe[qq * K + c0 + c] - acc[c]);
     }
     if (h2) {
         // factor column of o2 for the solves: C with its diagonal replaced by
@@ -628,7 +630,7 @@ __device__ __forceinline__ void bcr_level_item(const BcrDev &B, int s, int nact,
             const int a = q / nG, c = q % nG;
             double acc = 0.;
             for (int u = 0; u < K; ++u) acc = fma(Y2[u * GS + a], Y2[u * GS + c], acc);
-            bcr_st(&B.Zc[(size_t)o2 * nG * nG + q], acc);
+            st_sc1(&B.Zc[(size_t)o2 * nG * nG + q], acc);
         }
     }
     stamp(5);
@@ -665,11 +667,12 @@ __device__ __forceinline__ void bcr_root_wave(const BcrDev &B, int *fail, double
     for (int e = 0; e < nG * nG + (y ? nG : 0); ++e) {
         double v = 0.;
         if (e < nG * nG) {
-            for (int o = 1 + lane; o < B.nblk; o += 64) v += bcr_ld(&B.Zc[(size_t)o * nG * nG + e]);
+            for (int o = 1 + lane; o < B.nblk; o += 64) v += ld_sc1(&B.Zc[(size_t)o * nG * nG + e]);
         } else {
             const int q = e - nG * nG;
-            for (int o = 1 + lane; o < B.nblk; o += 64) v += bcr_ld(&B.gpart[(size_t)o * nG + q]);
+            for (int o = 1 + lane; o < B.nblk; o += 64) v += ld_sc1(&B.gpart[(size_t)o * nG + q]);
         }
+        // wave_sum written out: the call changes this kernel's instruction schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0) {
@@ -691,9 +694,9 @@ __device__ __forceinline__ void bcr_root_wave(const BcrDev &B, int *fail, double
         double v = 0.;
         if (q >= N * N) {
         } else if (i < K && c < K) {
-            v = c <= i ? bcr_ld(&D0[i * K + c]) : 0.;
+            v = c <= i ? ld_sc1(&D0[i * K + c]) : 0.;
         } else if (i >= K && i < n0 && c < K) {
-            v = bcr_ld(&B.Gk[(i - K) * K + c]);  // block 0 arrow
+            v = ld_sc1(&B.Gk[(i - K) * K + c]);  // block 0 arrow
         } else if (i >= K && i < n0 && c >= K && c <= i) {
             const int a = i - K, b = c - K;
             v = B.Gd[a * NGMAX + b] - zsum[a * nG + b];
@@ -791,7 +794,7 @@ __global__ void __launch_bounds__(64) k_bcr_fwd(BcrDev B, int s, int nact, doubl
 #pragma unroll
     for (int u = 0; u < K; ++u) {
         if (i == u) r *= cr[u];
-        const double y0 = bcr_rdlane(r, u), y1 = bcr_rdlane(r, 32 + u);
+        const double y0 = wave_rdlane(r, u), y1 = wave_rdlane(r, 32 + u);
         if (i > u) r = fma(-cr[u], h ? y1 : y0, r);
     }
     if (i < K) sy[h][i] = act ? r : 0.;
@@ -829,8 +832,7 @@ __global__ void __launch_bounds__(64) k_bcr_fwd_root(BcrDev B, const double *rw,
     for (int q = 0; q < nG; ++q) {  // lanes stride over the blocks (see k_bcr_root)
         double gs = 0.;
         for (int o = 1 + lane; o < B.nblk; o += 64) gs += B.gpart[(size_t)o * nG + q];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) gs += __shfl_xor(gs, off);
+        gs = wave_sum(gs);
         if (lane == 0) v[K + q] = rw[nb + q] - gs;
     }
     __syncthreads();
@@ -908,7 +910,7 @@ __global__ void __launch_bounds__(64) k_bcr_bwd(BcrDev B, int s, int nact, const
 #pragma unroll
     for (int u = K - 1; u >= 0; --u) {
         if (lane == u) v *= cc[u];
-        const double xu = bcr_rdlane(v, u);
+        const double xu = wave_rdlane(v, u);
         if (lane < u) v = fma(-cc[u], xu, v);
     }
     if (lane < K) {
@@ -927,28 +929,27 @@ __global__ void __launch_bounds__(64) k_bcr_bwd(BcrDev B, int s, int nact, const
 // stored write-through (agent-scope relaxed atomic stores), the storing
 // wave drains (vmcnt 0) and one lane stores the block's flag = epoch; a
 // consumer polls the producers' flags relaxed (s_sleep), then loads x with
-// sc1 loads (bcr_ld; no agent-scope acquire).  Factor rows and y (written by earlier
+// sc1 loads (ld_sc1; no agent-scope acquire).  Factor rows and y (written by earlier
 // launches) are loaded before the wait.  Every spin is bounded: a timeout
 // sets bit 1 of *fail (the solve then counts as failed) instead of hanging.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void bcr_put(double *x, int R, double v) {
-    __hip_atomic_store((bcr_gu64 *)(x + R), (unsigned long long)__double_as_longlong(v),
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    st_sc1(x + R, v);
 }
 
 __device__ __forceinline__ void bcr_publish(int *flags, int o, unsigned epoch, int lane) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0)
-        __hip_atomic_store((bcr_gu32 *)(flags + o), epoch, __ATOMIC_RELAXED,
+        __hip_atomic_store((gu32_t *)(flags + o), epoch, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // true when flags[a] (and flags[b], b >= 0) == epoch; false after the bound
 __device__ __forceinline__ bool bcr_wait(const int *flags, int a, int b, unsigned epoch) {
     for (unsigned spins = 0;; ++spins) {
-        unsigned fa = __hip_atomic_load((bcr_gu32 *)(flags + a), __ATOMIC_RELAXED,
+        unsigned fa = __hip_atomic_load((gu32_t *)(flags + a), __ATOMIC_RELAXED,
                                         __HIP_MEMORY_SCOPE_AGENT);
-        unsigned fb = b >= 0 ? __hip_atomic_load((bcr_gu32 *)(flags + b), __ATOMIC_RELAXED,
+        unsigned fb = b >= 0 ? __hip_atomic_load((gu32_t *)(flags + b), __ATOMIC_RELAXED,
                                                  __HIP_MEMORY_SCOPE_AGENT)
                              : epoch;
         fa = __builtin_amdgcn_readfirstlane(fa);
@@ -957,7 +958,7 @@ __device__ __forceinline__ bool bcr_wait(const int *flags, int a, int b, unsigne
         if (spins > (1u << 22)) return false;
         __builtin_amdgcn_s_sleep(2);
     }
-    // no agent-scope acquire: every x row is stored and loaded sc1 (bcr_ld);
+    // no agent-scope acquire: every x row is stored and loaded sc1 (ld_sc1);
     // the workgroup fence keeps the compiler from moving loads above the poll
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     return true;
@@ -1039,11 +1040,11 @@ __global__ void __launch_bounds__(64) k_bcr_bwd_all(BcrDev B, const double *y, d
             k = (int)(__builtin_amdgcn_readfirstlane(nxt) - tbase);
             continue;
         }
-        if (lane < K) {  // x rows of this launch's producers: sc1 loads (bcr_ld)
+        if (lane < K) {  // x rows of this launch's producers: sc1 loads (ld_sc1)
             xp[lane] = bcr_get_sc1(x, (o - s) * K + lane, nb);
             xn[lane] = hn ? bcr_get_sc1(x, (o + s) * K + lane, nb) : 0.;
         }
-        if (lane < nG) xg[lane] = bcr_ld(x + nb + lane);
+        if (lane < nG) xg[lane] = ld_sc1(x + nb + lane);
         __syncthreads();
         double v = 0.;
         if (lane < K) {
@@ -1056,7 +1057,7 @@ __global__ void __launch_bounds__(64) k_bcr_bwd_all(BcrDev B, const double *y, d
 #pragma unroll
         for (int u = K - 1; u >= 0; --u) {
             if (lane == u) v *= cc[u];
-            const double xu = bcr_rdlane(v, u);
+            const double xu = wave_rdlane(v, u);
             if (lane < u) v = fma(-cc[u], xu, v);
         }
         if (lane < K) {
@@ -1084,10 +1085,10 @@ __global__ void __launch_bounds__(64) k_bcr_bwd_all(BcrDev B, const double *y, d
 // Lin of level l-1).  Level 0 stages its operands from the band layout (no
 // k_bcr_load pass); the root waits for every item (the arrow sums).
 // Hand-off per MI355X guide G16 R1: every value read by another item is
-// stored write-through (bcr_st), each storing wave drains (vmcnt 0), the
+// stored write-through (st_sc1), each storing wave drains (vmcnt 0), the
 // workgroup barrier, one lane stores the item's flag = epoch; the consumer's
 // wave 0 polls its producers' flags relaxed (sc1), and the barrier releases
-// the other waves to load; every handed-off value is loaded sc1 (bcr_ld), so
+// the other waves to load; every handed-off value is loaded sc1 (ld_sc1), so
 // no agent-scope acquire is taken (MI355X guide, valid forms, first row).  Every spin is
 // bounded (timeout: bit 1 of *fail, the solve counts as failed).  Without
 // an arrow (nG = 0) the item publishes as soon as D_e, the new coupling and
@@ -1102,15 +1103,15 @@ __device__ __forceinline__ bool bcr_wait_items(const int *flags, int lo, int hi,
         for (unsigned spins = 0;; ++spins) {
             bool ok = true;
             if (i < hi)
-                ok = __hip_atomic_load((bcr_gu32 *)(flags + i), __ATOMIC_RELAXED,
+                ok = __hip_atomic_load((gu32_t *)(flags + i), __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT) == epoch;
             if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
             if (spins > (1u << 22)) return false;
             __builtin_amdgcn_s_sleep(2);
         }
     }
-    // no agent-scope acquire: every handed-off value is stored (bcr_st) and
-    // loaded (bcr_ld) sc1; the workgroup fence keeps the compiler from moving
+    // no agent-scope acquire: every handed-off value is stored (st_sc1) and
+    // loaded (ld_sc1) sc1; the workgroup fence keeps the compiler from moving
     // those loads above the poll
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     return true;
@@ -1179,7 +1180,7 @@ __global__ void __launch_bounds__(256) k_bcr_factor_df(BcrDev B, int *fail, cons
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) {
-            __hip_atomic_store((bcr_gu32 *)(B.fflags + it), epoch, __ATOMIC_RELAXED,
+            __hip_atomic_store((gu32_t *)(B.fflags + it), epoch, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
             if (trace) trace[4 * it + 3] = (long long)wall_clock64();
             it_s = (int)(nxt - tbase);

@@ -24,30 +24,6 @@ constexpr int BD_G0 = PCMAX;  // first arrow lane (12 + NGMAX 48 + rhs: 61 lanes
 constexpr int BD_R = BD_G0 + NGMAX;  // right-hand-side lane (after the widest arrow)
 static_assert(BD_R < 64, "arrow and right-hand-side lanes exceed the wave");
 
-// Augmented Cholesky of one block by one wave (bcr_chol_aug_wave's scheme
-// with a register-only column broadcast: PC <= 12 is short enough for
-// v_readlane per entry): lane i < PC holds row i of [S_b], every
-// right-hand-side lane holds its column; afterwards rows hold C and the
-// right-hand-side lanes (C^-1 b)^T.  Rows >= pc are identity padding.
-template <int PC>
-__device__ __forceinline__ void bd_chol_aug(double (&a)[PC], double &rsl, bool &bad) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int j = 0; j < PC; ++j) {
-        double d = wave_rdlane(a[j], j);
-        if (!(d > 0.) || !isfinite(d)) {
-            bad = true;
-            d = 1.;
-        }
-        const double rs = wave_rsq(d);
-        const double l = (lane > j) ? a[j] * rs : 0.;
-        a[j] = (lane == j) ? d * rs : (lane > j ? l : a[j]);
-        if (lane == j) rsl = rs;
-#pragma unroll
-        for (int c = j + 1; c < PC; ++c) a[c] = fma(-l, wave_rdlane(l, c), a[c]);
-    }
-}
-
 // Block b (camera-frame cf = B.blk_cf[b]) of S from the band layout, its
 // arrow columns and rhs; factor; store C (diagonal = 1/C_jj), Y_b and y_b;
 // the arrow partials Y_b^T Y_b, Y_b^T y_b.  One wave per block, four blocks
@@ -78,7 +54,7 @@ __global__ void __launch_bounds__(256) k_bd_factor(BdDev B, const double *__rest
     }
     double rsl = 0.;
     bool bad = false;
-    bd_chol_aug<PC>(a, rsl, bad);
+    wave_chol_aug<PC>(a, rsl, bad);
     if (bad && lane == 0) atomicOr(fail, 1);
     double *FC = B.FC + (size_t)b * PC * PC;
     if (lane < PC) {
@@ -104,8 +80,7 @@ __global__ void __launch_bounds__(256) k_bd_factor(BdDev B, const double *__rest
 #pragma unroll
             for (int c = 0; c < PC; ++c) my[NGMAX * PC + c] = a[c];
         }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_sync();
         for (int e = lane; e < nG * nG + nG; e += 64) {
             double acc = 0.;
             const int q = e < nG * nG ? e / nG : e - nG * nG;
@@ -243,9 +218,7 @@ __global__ void __launch_bounds__(64) k_bd_root(BdDev B, const double *__restric
 #pragma unroll
         for (int k = 0; k < RB; ++k) {
             const int e = e0 + k;
-            double w = v[k];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off);
+            const double w = wave_sum(v[k]);
             if (lane == 0 && e < ntot) {
                 if (e < nmat) zs[(e / nG) * NGMAX + e % nG] = w;
                 else gs[e - nmat] = w;
@@ -374,7 +347,7 @@ __global__ void __launch_bounds__(256) k_bd_direct(DevProblem P, BdDev B,
         }
         double rsl = 0.;
         bool bad = false;
-        bd_chol_aug<PC>(a, rsl, bad);
+        wave_chol_aug<PC>(a, rsl, bad);
         if (bad && lane == 0) atomicOr(fail, 1);
         double *FC = B.FC + (size_t)b * PC * PC;  // rows for the Newton forward solve
         if (lane < PC) {
@@ -403,8 +376,7 @@ __global__ void __launch_bounds__(256) k_bd_direct(DevProblem P, BdDev B,
             const double t = dk * acc;
             dn = t * t;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) dn += __shfl_xor(dn, off);
+        dn = wave_sum(dn);
     }
     if (lane == 0) wpart[wv] = dn;
     __syncthreads();
@@ -422,6 +394,8 @@ __global__ void __launch_bounds__(256) k_bd_direct(DevProblem P, BdDev B,
         s += __hip_atomic_load(&B.part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     red[threadIdx.x] = s;
     __syncthreads();
+    // block_tree written out: the call changes this kernel's instructions
+    // (the operands of each add swap places)
     for (int w = 128; w > 0; w >>= 1) {
         if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();

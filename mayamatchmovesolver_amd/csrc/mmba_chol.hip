@@ -264,6 +264,7 @@ __global__ void __launch_bounds__(256) k_trsv_fwd_all(const double *__restrict__
             const int c = q * 16 + t;
             s += Li[c] * rk[c];  // Linv is stored with zeros above the diagonal
         }
+        // the four lanes of a row (not wave_sum: 4 wide, ascending)
         s += __shfl_xor(s, 1, 64);
         s += __shfl_xor(s, 2, 64);
         if (q == 0) {
@@ -277,6 +278,7 @@ __global__ void __launch_bounds__(256) k_trsv_fwd_all(const double *__restrict__
             double u = 0.;
 #pragma unroll
             for (int t = 0; t < 16; ++t) u += L[q * 16 + t] * yk[q * 16 + t];
+            // four lanes, as above
             u += __shfl_xor(u, 1, 64);
             u += __shfl_xor(u, 2, 64);
             if (q == 0) r[I * TILE + row] -= u;

@@ -30,28 +30,9 @@
 
 #include "mmba_kernels.h"
 #include "mmba_plan.h"
+#include "mmba_wave_dev.h"
 
 namespace mmba {
-
-__device__ __forceinline__ double dn_rdlane(double v, int l) {
-    const long long x = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(x & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(x >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-__device__ __forceinline__ double dn_rsq(double d) {  // 1/sqrt(d), full fp64
-    double y = __builtin_amdgcn_rsq(d);
-    const double h = 0.5 * d;
-    y = y * fma(-h * y, y, 1.5);
-    y = y * fma(-h * y, y, 1.5);
-    return y;
-}
-
-__device__ __forceinline__ void dn_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // In-place Cholesky of the 64 x 64 diagonal block at A (column-major, ld)
 // and its inverse Linv (column-major 64 x 64, lower, ld 64), two waves in
@@ -82,12 +63,12 @@ __global__ void __launch_bounds__(128) k_dense_potf64(double *A, int ld, double 
     for (int j = 0; j < 64; ++j) {
         double l = 0.;
         if (wv == 0) {
-            double d = dn_rdlane(a[j], j);
+            double d = wave_rdlane(a[j], j);
             if (!(d > 0.) || !isfinite(d)) {
                 bad = 1;
                 d = 1.;
             }
-            const double rs = dn_rsq(d);
+            const double rs = wave_rsq(d);
             l = lane > j ? a[j] * rs : 0.;
             a[j] = lane == j ? d * rs : (lane > j ? l : a[j]);
             col[j & 1][lane] = l;
@@ -209,6 +190,7 @@ __global__ void __launch_bounds__(256) k_dense_bwd_step(const double *__restrict
                 s = fma(v[c].y, sx[8 * u + 2 * c + 1], s);
             }
         }
+        // the eight lanes of a column (not wave_sum: 8 wide, ascending)
         s += __shfl_xor(s, 1);
         s += __shfl_xor(s, 2);
         s += __shfl_xor(s, 4);

@@ -928,23 +928,6 @@ MMBA_DEV double fd_point(double v, double xmin, double xmax, int solver_type, do
     return v + h;
 }
 
-// Lane-level helpers of the one-wave factorisations (mmba_bdiag.hip,
-// mmba_batch.hip): fp64 rsqrt refined twice, v_readlane of a double.
-MMBA_DEV double wave_rsq(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-    const double h = 0.5 * d;
-    y = y * fma(-h * y, y, 1.5);
-    y = y * fma(-h * y, y, 1.5);
-    return y;
-}
-
-MMBA_DEV double wave_rdlane(double v, int l) {
-    const long long x = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(x & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(x >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // Unperturbed bundle position of observation (b, frame f): the bundle record
 // of a fast bundle, else the transform chain.
 MMBA_DEV void base_bundle(const DevProblem &P, int b, int f, double *bp) {

@@ -114,8 +114,6 @@ __global__ void k_rows_unpack(const double *__restrict__ recv, const int *__rest
     else if (k == 0 && i >= ga) xR[nb + (i - ga)] = v;
 }
 
-static int nblk(size_t n, int t) { return (int)((n + t - 1) / t); }
-
 // ---------------------------------------------------------------------------
 // Plan: sharded hand-back and step rows
 

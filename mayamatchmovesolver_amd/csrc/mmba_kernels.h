@@ -11,11 +11,11 @@ namespace mmba {
 // workgroup (the bundle columns of the reductions after the Jacobian)
 constexpr int NE_BND_TPB = 64;
 
-void launch_param_prep(hipStream_t s, const DevProblem &P, const double *x, double *ext,
-                       double *ext_pert, double *step, int solver_type, double delta,
-                       double eps_dif);
-void launch_set_attrs(hipStream_t s, const DevProblem &P, const double *ext);
-// launch_param_prep + launch_set_attrs in one launch
+// workgroups of bs threads that cover n items
+inline int nblk(long n, int bs) { return (int)((n + bs - 1) / bs); }
+
+// setParameters at x: external values, FD perturbations and steps, and the
+// attribute write of every parameter, one launch
 void launch_param_set(hipStream_t s, const DevProblem &P, const double *x, double *ext,
                       double *ext_pert, double *step, int solver_type, double delta,
                       double eps_dif);
@@ -80,9 +80,9 @@ void launch_jacobian_orec(hipStream_t s, const DevProblem &P, const ObjRecDev &O
                           const int *stale_param, double *eu, double *ed);
 int residual_blocks(const DevProblem &P);
 // Partial count of the trial point's residual pass (launch_residual_jp):
-// one per camera-frame where trial_cf_fusable, else residual_blocks.
+// one per camera-frame on the uniform fast plans of the fused Jacobian pass
+// (unless trial_cf_off), else residual_blocks.
 bool &trial_cf_off();
-bool trial_cf_fusable(const DevProblem &P);
 int trial_blocks(const DevProblem &P);
 // Reductions: with a ticket (a zero-initialised device counter) the partial
 // sums are combined inside the same launch, otherwise by a second kernel.
@@ -97,7 +97,7 @@ void launch_residual(hipStream_t s, const DevProblem &P, const double *recs, dou
 void launch_dist_stats(hipStream_t s, const DevProblem &P, const double *ed, double *partial,
                        int nparts, int rstride, double *out);
 // launch_residual (partials only) plus ||J p||^2 partials of the same blocks
-// into partial_jp (k_jp_sumsq's sum, one launch)
+// into partial_jp (lmder's ||J p||^2 for prered, one launch)
 void launch_residual_jp(hipStream_t s, const DevProblem &P, const double *recs, double *f,
                         double *eu, double *ed, double *partial, const double *J,
                         const int *jcol, const int *nloc, const double *pstep,
@@ -300,7 +300,7 @@ bool launch_schur_dest(hipStream_t s, const DevProblem &P, const double *W, cons
                        const int *wave_list = nullptr, int n_wave = 0,
                        const int *lane_list = nullptr, int n_lane = 0);
 void launch_schur_rhs(hipStream_t s, const DevProblem &P, const double *W, const double *tb,
-                      const int *row_cf, double *rhs);
+                      double *rhs);
 void launch_schur_glob(hipStream_t s, const DevProblem &P, const double *W, const double *Wg,
                        const double *tb, const SView &V, double *rhs);
 void launch_backsub_bundle(hipStream_t s, const DevProblem &P, const double *W, const double *Wg,
@@ -422,23 +422,10 @@ void launch_sumsq_div(hipStream_t s, const double *a, const double *d, int n, do
 void launch_sumsq_mix(hipStream_t s, const double *y, const double *v, int n, double *partial,
                       int nparts, double *out, const int *mask);
 void launch_reduce_sum(hipStream_t s, const double *partial, int n, double *out);
-void launch_gnorm(hipStream_t s, const double *g, const double *acnorm, int n, double fnorm,
-                  double *partial, int nparts, double *out, const int *mask = nullptr,
-                  unsigned int *ticket = nullptr);
-void launch_jp_sumsq(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
-                     const int *nloc, const double *p, double *partial, int nparts,
-                     double *out, unsigned int *ticket = nullptr);
-void launch_zero_flag(hipStream_t s, const double *acnorm, int n, const int *mask,
-                      double *partial, int nparts, double *out, unsigned int *ticket = nullptr);
 // *out = (*flag != 0) as a double (fail flags joining the scalar reads);
 // the flag is cleared for the next use
 void launch_flag_to_scalar(hipStream_t s, int *flag, double *out);
 void launch_keep_rows(hipStream_t s, double *v, int lo, int hi, int nCF, int nR, int root);
-void launch_keep_mask(hipStream_t s, const double *src, const int *mask, int n, double *dst);
-void launch_lm_step(hipStream_t s, int n, const double *xs, const double *x, const double *diag,
-                    double *wa1, double *wa2, double *wa3);
-void launch_diag_init(hipStream_t s, int n, const double *acnorm, double *diag, int first,
-                      int mode);
 void launch_newton_v(hipStream_t s, int n, const double *diag, const double *x, double dxnorm,
                      double *v);
 // unsharded hand-back into host-mapped page-locked lists (k_handback_host)

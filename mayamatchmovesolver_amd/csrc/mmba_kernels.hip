@@ -83,7 +83,8 @@ __device__ __forceinline__ void bundle_chol3(double (&A)[3][3], double (&rhs)[3]
 
 // reduce_row_block by one wave (a 64-thread workgroup of another launch):
 // lane t holds the block's threads t, t + 64, t + 128 and t + 192 and combines
-// them, then the lanes, in that block's tree order -- the same value.
+// them, then the lanes, in block_tree's order (mmba_wave_dev.h; __shfl_down
+// stands for its levels w = 32 ... 1) -- the same value.
 // In two steps, so that a caller can put other loads between them: row_issue
 // issues every load of a row of up to 1,536 entries (C4: 1,282) into q,
 // row_finish combines them (a longer row is loaded there, in turn).
@@ -257,14 +258,6 @@ __device__ __forceinline__ void set_attr_one(const DevProblem &P, int p, double 
     P.attr_val[P.p_vidx[p]] = value;
 }
 
-__global__ void k_param_prep(DevProblem P, const double *__restrict__ x, double *ext,
-                             double *ext_pert, double *step, int solver_type, double delta,
-                             double eps_dif) {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P.n) return;
-    param_prep_one(P, p, x[p], ext, ext_pert, step, solver_type, delta, eps_dif);
-}
-
 // Central differences, second evaluation of each column
 // (solveFunc_calculateJacobianMatrixForParameter, adjust_solveFunc.cpp:405-475):
 // deltaB = calculateParameterDelta(value, delta, -1); when deltaB == deltaA the
@@ -297,14 +290,8 @@ __global__ void k_param_central(DevProblem P, const double *__restrict__ x, doub
     atomicAdd(count, 1.0);
 }
 
-__global__ void k_set_attrs(DevProblem P, const double *__restrict__ ext) {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P.n) return;
-    set_attr_one(P, p, ext[p]);
-}
-
 // setParameters in one launch: external value, FD perturbation and the
-// attribute write of each parameter (k_param_prep + k_set_attrs).
+// attribute write of each parameter (param_prep_one + set_attr_one).
 __global__ void k_param_set(DevProblem P, const double *__restrict__ x, double *ext,
                             double *ext_pert, double *step, int solver_type, double delta,
                             double eps_dif) {
@@ -494,6 +481,7 @@ __global__ void __launch_bounds__(256) k_residual_jp_cf(
     red[0][tid] = s;
     red[1][tid] = sj;
     __syncthreads();
+    // block_tree's levels for both rows at once (one barrier per level, not two)
     for (int w = 128; w > 0; w >>= 1) {
         if (tid < w) {
             red[0][tid] += red[0][tid + w];
@@ -948,6 +936,7 @@ __device__ __forceinline__ void ne_cf_u_body(const DevProblem &P, const double *
 #pragma unroll
     for (int e = 0; e < NT; ++e) {
         double v = acc[e];
+        // wave_sum written out: the call changes this kernel's instruction schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0) wsum[wv][e] = v;
@@ -1045,6 +1034,7 @@ __global__ void __launch_bounds__(64 * NW) k_ne_cf_split(DevProblem P, const dou
 #pragma unroll
     for (int e = 0; e < NT; ++e) {
         double v = acc[e];
+        // wave_sum written out: the call changes this kernel's instruction schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0) wsum[wv][e] = v;
@@ -1342,6 +1332,7 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         double v = acc[e];
+        // wave_sum written out: the call changes this kernel's instruction schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0) wsum[wv][e] = v;
@@ -1504,6 +1495,8 @@ __global__ void __launch_bounds__(NE_BND_TPB) k_ne_bnd_jb(DevProblem P, double *
     red[1][threadIdx.x] = xn;
     red[2][threadIdx.x] = gm;
     __syncthreads();
+    // not block_tree: three rows (max, sum, max) over NE_BND_TPB threads, one
+    // barrier per level for all of them
     for (int w = NE_BND_TPB / 2; w > 0; w >>= 1) {
         if (threadIdx.x < w) {
             red[0][threadIdx.x] = fmax(red[0][threadIdx.x], red[0][threadIdx.x + w]);
@@ -1648,6 +1641,7 @@ __device__ __forceinline__ void ne_glob_body(const DevProblem &P, const double *
 #pragma unroll
     for (int e = 0; e < NA; ++e) {
         double v = accv[e];
+        // wave_sum written out: the call changes this kernel's instruction schedule
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0) wsum[wave][e] = v;
@@ -1762,8 +1756,7 @@ __global__ void __launch_bounds__(256) k_ne_glob_reduce(DevProblem P,
         const bool mat = t < nG * nG;
         double s = 0.;
         for (int k = lane; k < nblk; k += 64) s += partial[(size_t)k * NA + t];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        s = wave_sum(s);
         if (lane == 0) {
             if (mat)
                 Agg[(t / nG) * NGMAX + t % nG] = s;
@@ -1798,32 +1791,27 @@ __global__ void k_colnorms(DevProblem P, const double *__restrict__ Acc,
     acnorm[p] = sqrt(d);
 }
 
-// Block tree reduction of one value per thread into partial[blockIdx.x]
-// (the order of k_sumsq / k_gnorm / k_zero_flag: bit-identical partials).
+// One value per thread through block_tree into partial[blockIdx.x].
 template <bool MAX>
 __device__ __forceinline__ void block_partial(double v, double *red, double *partial) {
     red[threadIdx.x] = v;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w)
-            red[threadIdx.x] = MAX ? fmax(red[threadIdx.x], red[threadIdx.x + w])
-                                   : red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree(red, MAX);
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
 // lmder bookkeeping after a Jacobian evaluation in one pass over the
 // parameters (lmder.c after qrfac; MINPACK's rank test):
 //   acnorm_p = sqrt(A_pp) and g_p of global parameters (k_colnorms);
-//   partial row 0: max over owned p of [acnorm_p == 0]           (k_zero_flag)
+//   partial row 0: max over owned p of [acnorm_p == 0] (the zero-column flag)
 //   diag update: mode 1, first pass diag = acnorm (1 where 0), then
-//   diag = max(diag, acnorm)                                      (k_diag_init)
-//   partial row 1: sum over owned p of (diag_p x_p)^2, do_xn      (xnorm)
+//   diag = max(diag, acnorm)
+//   partial row 1: sum over owned p of (diag_p x_p)^2, do_xn (xnorm)
 //   partial row 2: max over owned p with acnorm_p != 0 of
-//   |g_p / fnorm| / acnorm_p, do_gn                               (k_gnorm)
-// Rows are rstride apart, nparts = gridDim.x blocks each; every thread
-// accumulates in the grid-stride order of the separate kernels.
+//   |g_p / fnorm| / acnorm_p, do_gn (gnorm)
+// Rows are rstride apart, nparts = gridDim.x blocks each; thread t of block b
+// accumulates p = b * 256 + t, then every gridDim.x * 256-th in ascending
+// order, and each row goes through block_tree.
 __global__ void __launch_bounds__(256) k_jac_epilogue(
     DevProblem P, const double *__restrict__ Acc, const double *__restrict__ Abb,
     const double *__restrict__ Agg, const double *__restrict__ gG, double *acnorm, double *g,
@@ -1896,9 +1884,9 @@ __global__ void __launch_bounds__(256) k_jac_epilogue(
 }
 
 // lmder trial point in one pass over the parameters: p = -xs,
-// wa1 = p, wa2 = x + p, wa3 = diag p (k_lm_step); setParameters at wa2
-// (k_param_prep + k_set_attrs); partial rows: 0 = sum (diag p)^2 (pnorm),
-// 1 = sum (diag wa2)^2 (the candidate ||D x||), over owned p.
+// wa1 = p, wa2 = x + p, wa3 = diag p; setParameters at wa2 (param_prep_one +
+// set_attr_one); partial rows: 0 = sum (diag p)^2 (pnorm), 1 = sum (diag
+// wa2)^2 (the candidate ||D x||), over owned p in k_jac_epilogue's order.
 __global__ void __launch_bounds__(256) k_trial_prep(
     DevProblem P, const double *__restrict__ xs, const double *__restrict__ x,
     const double *__restrict__ diag, double *wa1, double *wa2, double *wa3, double *ext,
@@ -1935,9 +1923,9 @@ __device__ void lm_decide(const LmDec &d, double *scalar) {
     lm_publish(d, lm_decide_vals(d, v), scalar);
 }
 
-// Several partial rows reduced in one launch, block r for row r, in the
-// order of k_reduce_sum / k_reduce_max; block 0 also converts the
-// factorisation fail flag to a scalar and clears it (k_flag_to_scalar).
+// Several partial rows reduced in one launch, block r for row r
+// (reduce_row_block); block 0 also converts the factorisation fail flag to a
+// scalar and clears it (k_flag_to_scalar).
 // host (optional): the last block to finish copies scalar[0, host_n) into
 // that page-locked host mirror (the LM control thread's slots), so the
 // decision point needs no separate device-to-host copy launch.
@@ -2640,8 +2628,7 @@ __global__ void __launch_bounds__(64) k_schur_rhs(DevProblem P, const double *__
     for (int a = 0; a < PCMAX; ++a) {
         if (a >= pc) break;
         double v = acc[a];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        v = wave_sum(v);
         if (threadIdx.x == 0) rhs[r0 + a] -= v;
     }
 }
@@ -2968,7 +2955,8 @@ __global__ void __launch_bounds__(64) k_backsub_trial(DevProblem P, const double
             trial_one(P, T, j, x[j], pn, xn);
         }
     }
-    // one partial per workgroup, 64-lane fixed tree
+    // one partial per workgroup, 64-lane fixed tree (not block_tree: 64 wide,
+    // both sums per level)
     red[threadIdx.x] = pn;
     red[64 + threadIdx.x] = xn;
     __syncthreads();
@@ -3305,6 +3293,7 @@ __global__ void __launch_bounds__(64) k_trial_prep_rec(DevProblem P, const doubl
             trial_one(P, T, j, xs[j], pn, xn);
         }
     }
+    // the 64-leaf fixed tree of k_backsub_trial
     red[threadIdx.x] = pn;
     red[64 + threadIdx.x] = xn;
     __syncthreads();
@@ -3371,8 +3360,7 @@ __global__ void __launch_bounds__(256) k_newton_glob(DevProblem P, const double 
     __shared__ double red[4];
     double acc = 0.;
     for (int b = threadIdx.x; b < P.nB; b += 256) acc += gp[(size_t)q * P.nB + b];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) wR[P.nR - P.nG + q] -= (red[0] + red[1]) + (red[2] + red[3]);
@@ -3395,8 +3383,10 @@ __global__ void k_gather_R(DevProblem P, const double *__restrict__ v, double *v
 // Vector helpers and deterministic reductions.  With a ticket the reduction
 // finishes in the same launch: every block publishes its partial (release),
 // takes a ticket, and the last block to arrive (acquire) combines all
-// partials in the same fixed order as the separate k_reduce_* kernel, then
-// resets the ticket (so the result is bit-identical to the two-launch form).
+// partials in k_reduce_sum's order (thread t adds partials t, t + 256, ...,
+// then block_tree), then resets the ticket (so the result is bit-identical
+// to the two-launch form).  The kernels below share one shape: a grid-stride
+// accumulate per thread, block_tree, then a plain store or finish_blocks.
 // -------------------------------------------------------------------------
 
 __global__ void __launch_bounds__(256) k_sumsq(const double *__restrict__ a,
@@ -3412,10 +3402,7 @@ __global__ void __launch_bounds__(256) k_sumsq(const double *__restrict__ a,
     }
     red[threadIdx.x] = s;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree(red);
     finish_blocks<false>(red[0], partial, out, ticket);
 }
 
@@ -3434,10 +3421,7 @@ __global__ void __launch_bounds__(256) k_sumsq_mix(const double *__restrict__ y,
     }
     red[threadIdx.x] = s;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree(red);
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
@@ -3454,10 +3438,7 @@ __global__ void __launch_bounds__(256) k_sumsq_div(const double *__restrict__ a,
     }
     red[threadIdx.x] = s;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree(red);
     finish_blocks<false>(red[0], partial, out, ticket);
 }
 
@@ -3468,92 +3449,8 @@ __global__ void __launch_bounds__(256) k_reduce_sum(const double *__restrict__ p
     for (int i = threadIdx.x; i < n; i += blockDim.x) s += partial[i];
     red[threadIdx.x] = s;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree(red);
     if (threadIdx.x == 0) *out = red[0];
-}
-
-// gnorm (lmder.c): max_l |g_l / fnorm| / acnorm_l over acnorm_l != 0.
-__global__ void __launch_bounds__(256) k_gnorm(const double *__restrict__ g,
-                                               const double *__restrict__ acnorm, int n,
-                                               double fnorm, const int *__restrict__ mask,
-                                               double *partial, double *out,
-                                               unsigned int *ticket) {
-    __shared__ double red[256];
-    double m = 0.;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        if (own_mask(mask, i) && acnorm[i] != 0.) m = fmax(m, fabs((g[i] / fnorm) / acnorm[i]));
-    }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    finish_blocks<true>(red[0], partial, out, ticket);
-}
-
-__global__ void k_reduce_max(const double *__restrict__ partial, int n, double *out) {
-    __shared__ double red[256];
-    double m = 0.;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmax(m, partial[i]);
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = red[0];
-}
-
-// ||J p||^2 partial sums (prered in lmder): (J p)_obs = sum_l J_l p[jcol_l].
-__global__ void __launch_bounds__(256) k_jp_sumsq(DevProblem P, const double *__restrict__ J,
-                                                  const int *__restrict__ jcol,
-                                                  const int *__restrict__ nloc,
-                                                  const double *__restrict__ p,
-                                                  double *partial, double *out,
-                                                  unsigned int *ticket) {
-    __shared__ double red[256];
-    const int M = P.M;
-    double s = 0.;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) {
-        if (!own_obs(P, i)) continue;
-        double ax = 0., ay = 0.;
-        const int nl = nloc[i];
-        for (int l = 0; l < nl; ++l) {
-            const double pv = p[jcol[(size_t)l * M + i]];
-            ax += J[(size_t)(2 * l) * M + i] * pv;
-            ay += J[(size_t)(2 * l + 1) * M + i] * pv;
-        }
-        s += ax * ax + ay * ay;
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    finish_blocks<false>(red[0], partial, out, ticket);
-}
-
-// max over owned entries of [acnorm_j == 0] (MINPACK's rank test, nsing < n).
-__global__ void __launch_bounds__(256) k_zero_flag(const double *__restrict__ acnorm, int n,
-                                                   const int *__restrict__ mask,
-                                                   double *partial, double *out,
-                                                   unsigned int *ticket) {
-    __shared__ double red[256];
-    double m = 0.;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        if (own_mask(mask, i) && acnorm[i] == 0.) m = 1.;
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    finish_blocks<true>(red[0], partial, out, ticket);
 }
 
 // Keep this shard's reduced-system rows [lo, hi) (and the global rows on the
@@ -3563,34 +3460,6 @@ __global__ void k_keep_rows(double *v, int lo, int hi, int nCF, int nR, int root
     if (r >= nR) return;
     const bool keep = (r >= nCF) ? root != 0 : (r >= lo && r < hi);
     if (!keep) v[r] = 0.;
-}
-
-// dst = mask ? src : 0
-__global__ void k_keep_mask(const double *__restrict__ src, const int *__restrict__ mask, int n,
-                            double *dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = own_mask(mask, i) ? src[i] : 0.;
-}
-
-// Elementwise LM vector updates.
-__global__ void k_lm_step(int n, const double *__restrict__ xs, const double *__restrict__ x,
-                          const double *__restrict__ diag, double *wa1, double *wa2,
-                          double *wa3) {
-    // wa1 = -xs (step), wa2 = x + wa1, wa3 = diag * wa1
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const double s = -xs[j];
-    wa1[j] = s;
-    wa2[j] = x[j] + s;
-    wa3[j] = diag[j] * s;
-}
-
-__global__ void k_diag_init(int n, const double *__restrict__ acnorm, double *diag, int first,
-                            int mode) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    if (first && mode != 2) diag[j] = acnorm[j] == 0. ? 1. : acnorm[j];
-    if (mode != 2) diag[j] = fmax(diag[j], acnorm[j]);
 }
 
 __global__ void k_newton_v(int n, const double *__restrict__ diag, const double *__restrict__ x,
@@ -3668,7 +3537,6 @@ __global__ void __launch_bounds__(256) k_handback_host(int Mg, int nrows,
 // =========================================================================
 namespace mmba {
 
-static inline int nblk(long n, int bs) { return (int)((n + bs - 1) / bs); }
 bool trial_records_ok(const DevProblem &P) {
     return P.nG == 0 && P.cf_aidx != nullptr && !P.rs && P.ncf > 0;
 }
@@ -3709,13 +3577,6 @@ void launch_obs_wtx(hipStream_t s, const DevProblem &P, const double *W, const d
     k_obs_wtx<<<nblk(P.M, 64), 64, sizeof(double) * 64 * P.wst, s>>>(P, W, xR, U);
 }
 
-void launch_param_prep(hipStream_t s, const DevProblem &P, const double *x, double *ext,
-                       double *ext_pert, double *step, int solver_type, double delta,
-                       double eps_dif) {
-    if (P.n == 0) return;
-    k_param_prep<<<nblk(P.n, 256), 256, 0, s>>>(P, x, ext, ext_pert, step, solver_type, delta,
-                                                 eps_dif);
-}
 void launch_records(hipStream_t s, const DevProblem &P, const int *var_cf,
                     const double *ext_pert, const double *step, double *recs, int nvar,
                     double *brec, int base_only, const ObjRecDev *O) {
@@ -3759,16 +3620,13 @@ void launch_reduce_multi(hipStream_t s, const double *partial, const RedSpec &sp
         k_reduce_multi<<<spec.nrows, 256, 0, s>>>(partial, spec, scalar, flag, host, host_n,
                                                    ticket, host_seq, seq, dec);
 }
-void launch_set_attrs(hipStream_t s, const DevProblem &P, const double *ext) {
-    k_set_attrs<<<nblk(P.n, 256), 256, 0, s>>>(P, ext);
-}
 // Partial sums of a residual evaluation: one per 256 observations, plus one
 // for the attribute rows (k_rows_eval writes entry nblk(M, 256)).
 int residual_blocks(const DevProblem &P) { return nblk(P.M, 256) + (P.nrows > 0 ? 1 : 0); }
 // The trial point's residual pass runs per camera-frame (k_residual_jp_cf)
 // on the uniform fast plans of the fused K2: no attribute rows, no lens, no
 // rolling shutter, implicit Jacobian columns.
-bool trial_cf_fusable(const DevProblem &P) {
+static bool trial_cf_fusable(const DevProblem &P) {
     return jac_ne_fusable(P, P.pc_uniform) && P.all_bnd_fast && P.no_lens && P.jcol_implicit &&
            !trial_cf_off();
 }
@@ -3885,6 +3743,7 @@ __global__ void __launch_bounds__(256) k_dist_stats(DevProblem P, const double *
     red[1][threadIdx.x] = nmn;
     red[2][threadIdx.x] = mx;
     __syncthreads();
+    // block_tree's levels for three rows (sum, max, max) at once, one barrier per level
     for (int w = 128; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w) {
             red[0][threadIdx.x] += red[0][threadIdx.x + w];
@@ -3913,6 +3772,7 @@ __global__ void __launch_bounds__(256) k_dist_stats_fin(const double *__restrict
     red[1][threadIdx.x] = nmn;
     red[2][threadIdx.x] = mx;
     __syncthreads();
+    // block_tree's levels for three rows (sum, max, max) at once, one barrier per level
     for (int w = 128; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w) {
             red[0][threadIdx.x] += red[0][threadIdx.x + w];
@@ -4053,6 +3913,7 @@ void launch_param_central(hipStream_t s, const DevProblem &P, const double *x, d
 // B = [0 1; 1 s], s = ||f||^2, and J^T f = u + s c.  One workgroup per call,
 // fixed-order sums (bit-reproducible); the vectors are n long.
 // ---------------------------------------------------------------------------
+// not block_tree: 1024 threads, NV sums per level
 template <int NV>
 __device__ __forceinline__ void b15_block_sum(double (&v)[NV], double (*red)[1024]) {
     const int tid = threadIdx.x;
@@ -4514,8 +4375,7 @@ bool launch_schur_dest(hipStream_t s, const DevProblem &P, const double *W, cons
     return false;
 }
 void launch_schur_rhs(hipStream_t s, const DevProblem &P, const double *W, const double *tb,
-                      const int *row_cf, double *rhs) {
-    (void)row_cf;
+                      double *rhs) {
     if (P.ncf > 0) k_schur_rhs<<<P.ncf, 64, 0, s>>>(P, W, tb, rhs);
 }
 void launch_schur_glob(hipStream_t s, const DevProblem &P, const double *W, const double *Wg,
@@ -4571,23 +4431,6 @@ void launch_sumsq_mix(hipStream_t s, const double *y, const double *v, int n, do
 void launch_reduce_sum(hipStream_t s, const double *partial, int n, double *out) {
     k_reduce_sum<<<1, 256, 0, s>>>(partial, n, out);
 }
-void launch_gnorm(hipStream_t s, const double *g, const double *acnorm, int n, double fnorm,
-                  double *partial, int nparts, double *out, const int *mask,
-                  unsigned int *ticket) {
-    k_gnorm<<<nparts, 256, 0, s>>>(g, acnorm, n, fnorm, mask, partial, out, ticket);
-    if (!ticket) k_reduce_max<<<1, 256, 0, s>>>(partial, nparts, out);
-}
-void launch_jp_sumsq(hipStream_t s, const DevProblem &P, const double *J, const int *jcol,
-                     const int *nloc, const double *p, double *partial, int nparts,
-                     double *out, unsigned int *ticket) {
-    k_jp_sumsq<<<nparts, 256, 0, s>>>(P, J, jcol, nloc, p, partial, out, ticket);
-    if (!ticket && out) k_reduce_sum<<<1, 256, 0, s>>>(partial, nparts, out);
-}
-void launch_zero_flag(hipStream_t s, const double *acnorm, int n, const int *mask,
-                      double *partial, int nparts, double *out, unsigned int *ticket) {
-    k_zero_flag<<<nparts, 256, 0, s>>>(acnorm, n, mask, partial, out, ticket);
-    if (!ticket) k_reduce_max<<<1, 256, 0, s>>>(partial, nparts, out);
-}
 __global__ void k_flag_to_scalar(int *flag, double *out) {
     if (threadIdx.x == 0) {
         *out = (double)*flag;
@@ -4599,17 +4442,6 @@ void launch_flag_to_scalar(hipStream_t s, int *flag, double *out) {
 }
 void launch_keep_rows(hipStream_t s, double *v, int lo, int hi, int nCF, int nR, int root) {
     if (nR > 0) k_keep_rows<<<nblk(nR, 256), 256, 0, s>>>(v, lo, hi, nCF, nR, root);
-}
-void launch_keep_mask(hipStream_t s, const double *src, const int *mask, int n, double *dst) {
-    if (n > 0) k_keep_mask<<<nblk(n, 256), 256, 0, s>>>(src, mask, n, dst);
-}
-void launch_lm_step(hipStream_t s, int n, const double *xs, const double *x, const double *diag,
-                    double *wa1, double *wa2, double *wa3) {
-    k_lm_step<<<nblk(n, 256), 256, 0, s>>>(n, xs, x, diag, wa1, wa2, wa3);
-}
-void launch_diag_init(hipStream_t s, int n, const double *acnorm, double *diag, int first,
-                      int mode) {
-    k_diag_init<<<nblk(n, 256), 256, 0, s>>>(n, acnorm, diag, first, mode);
 }
 void launch_newton_v(hipStream_t s, int n, const double *diag, const double *x, double dxnorm,
                      double *v) {

@@ -5,7 +5,7 @@
 // src/mmSolver/adjust/adjust_cminpack_lmder.cpp:94-184):
 //   qrfac column norms acnorm_j       -> sqrt(A_jj), A = J^T J
 //   R^T (Q^T f)                       -> g = J^T f
-//   ||R P^T p||                       -> ||J p|| (k_jp_sumsq, exact products)
+//   ||R P^T p||                       -> ||J p|| (exact products, summed in the trial residual pass)
 //   qrsolv(par): (A + par D^2) x = g  -> bundle-Schur + tiled Cholesky
 //   ||S^-T P^T v|| in lmpar           -> sqrt(v^T (A + par D^2)^-1 v)
 //                                        = ||Lb^-1 v_b|| (+) ||Ls^-1 w_R||
@@ -802,7 +802,7 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
                     launch_schur_dest(s, PS, d_W, d_dest, d_dest_off, ndest, d_dpairs, V,
                                       pc_uniform, band && bs.use_bcr && !rs_bnd, d_tb, d_rhs, fi,
                                       d_dest_wave, n_dest_wave, d_dest_lane, n_dest_lane);
-                if (!rhs_done) launch_schur_rhs(s, PS, d_W, d_tb, d_row_cf, d_rhs);
+                if (!rhs_done) launch_schur_rhs(s, PS, d_W, d_tb, d_rhs);
                 launch_schur_glob(s, PS, d_W, d_Wg, d_tb, V, d_rhs);
             } else {
                 launch_schur_pairs(s, PS, d_W, d_Wg, d_tb, V, d_rhs);

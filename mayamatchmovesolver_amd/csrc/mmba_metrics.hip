@@ -42,7 +42,8 @@ __device__ __forceinline__ void metrics_group(const MetricsDev &T, const double 
             pos = p;
         }
     }
-    // every lane of the wave takes part (dead groups carry zeros)
+    // every lane of the wave takes part (dead groups carry zeros); not
+    // wave_sum: W lanes, ascending, with the arg-max folded in
 #pragma unroll
     for (int d = 1; d < W; d <<= 1) {
         const double s2 = __shfl_xor(sum, d), m2 = __shfl_xor(mx, d);

@@ -61,7 +61,6 @@ void launch_obj_records(hipStream_t s, const DevProblem &P, const ObjRecDev &O,
 
 // The record-reading instantiations of k_residual / k_jacobian
 // (mmba_obs_dev.h), in this translation unit only.
-static inline int nblk(long n, int bs) { return (int)((n + bs - 1) / bs); }
 
 void launch_residual_orec(hipStream_t s, const DevProblem &P, const ObjRecDev &O,
                           const double *recs, double *f, double *eu, double *ed, double *partial,

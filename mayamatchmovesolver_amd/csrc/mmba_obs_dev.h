@@ -11,6 +11,7 @@
 
 #include "mmba_geom.h"
 #include "mmba_kernels.h"
+#include "mmba_wave_dev.h"
 
 namespace mmba {
 
@@ -48,12 +49,7 @@ __device__ __forceinline__ void finish_blocks(double v, double *partial, double 
     }
     red[threadIdx.x] = a;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w)
-            red[threadIdx.x] = MAX ? fmax(red[threadIdx.x], red[threadIdx.x + w])
-                                   : red[threadIdx.x] + red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree(red, MAX);
     if (threadIdx.x == 0) {
         *out = red[0];
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -65,8 +61,8 @@ __device__ __forceinline__ void finish_blocks(double v, double *partial, double 
 // distance, and one partial sum of squares per block.
 // -------------------------------------------------------------------------
 // JP: the trial-point evaluation also forms (J p)_obs = sum_l J_l p[jcol_l]
-// from the Jacobian blocks of the current x (lmder's ||J p|| for prered,
-// k_jp_sumsq) into a second partial row.
+// from the Jacobian blocks of the current x (lmder's ||J p|| for prered)
+// into a second partial row.
 // FAST: every bundle is fast and no camera has a lens (the transform-chain
 // and lens code, and their registers, are compiled out).
 // RS: rolling shutter (mmba_rs.hip): each observation's camera record is
@@ -181,6 +177,8 @@ __global__ void __launch_bounds__(256) k_residual(DevProblem P, const double *__
     if constexpr (JP) {
         red[threadIdx.x] = sj;
         __syncthreads();
+        // block_tree written out (as below): the call changes this kernel's
+        // instructions (the operands of each add swap places)
         for (int w = 128; w > 0; w >>= 1) {
             if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
             __syncthreads();

@@ -487,6 +487,7 @@ __global__ void __launch_bounds__(64) k_pcr_rhs(PcrDev P, const double *__restri
         for (int i = 0; i < K; ++i) z = fma(lg[i * K + lane], srho[i], z);
     }
     double v = (lane < K && R < nb && mask[R]) ? w0 * z : 0.;
+    // wave_sum written out: the call changes this kernel's instruction schedule
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if (lane == 0) part[j] = v;

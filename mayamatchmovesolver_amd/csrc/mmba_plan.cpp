@@ -1280,9 +1280,6 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     if (pc_uniform < 0) pc_uniform = 0;
     // ---- Schur accumulation plan: observation pairs sharing a bundle, sorted
     // by destination block (cf_i >= cf_j) ----
-    std::vector<int> row_cf(nCF > 0 ? nCF : 1, 0);
-    for (int cf = 0; cf < ncf; ++cf)
-        for (int a = 0; a < cf_pc[cf]; ++a) row_cf[cf_roff[cf] + a] = cf;
     std::vector<int2> dest_h, dpairs_h;
     std::vector<int> dest_off_h;
     {
@@ -1840,7 +1837,6 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     d_pairs = upload(pairs);
     d_rows_off = upload(panel_rows_off);
     d_cols_off = upload(panel_cols_off);
-    d_row_cf = upload(row_cf);
     if (use_dest) {
         d_dest = upload(dest_h);
         d_dest_off = upload(dest_off_h);

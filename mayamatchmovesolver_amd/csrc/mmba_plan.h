@@ -157,7 +157,7 @@ struct Plan {
     // wave list, k_schur_dest_lane over the lane list); null: one pass
     int *d_dest_wave = nullptr, *d_dest_lane = nullptr;
     int n_dest_wave = 0, n_dest_lane = 0;
-    int *d_dest_off = nullptr, *d_row_cf = nullptr;
+    int *d_dest_off = nullptr;
     // band + arrow layout of the reduced system (mmba_band.hip)
     bool band = false;
     int bw = 0;

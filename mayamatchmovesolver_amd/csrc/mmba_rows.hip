@@ -58,6 +58,7 @@ __global__ void __launch_bounds__(64) k_rows_eval(DevProblem P, double *fr, doub
     red[0][threadIdx.x] = s;
     red[1][threadIdx.x] = sj;
     __syncthreads();
+    // two rows of 64 at once, w = 32 ... 1 (k_backsub_trial's tree)
     for (int w = 32; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w) {
             red[0][threadIdx.x] += red[0][threadIdx.x + w];

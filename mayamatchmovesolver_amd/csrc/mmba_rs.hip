@@ -30,7 +30,6 @@ namespace mmba {
 #define MMBA_RS_WAVES 1
 #endif
 
-static inline int nblk_rs(long n, int bs) { return (int)((n + bs - 1) / bs); }
 
 __device__ __forceinline__ long long param_vidx(const DevProblem &P, int p) { return P.p_vidx[p]; }
 
@@ -417,6 +416,7 @@ __global__ void __launch_bounds__(256) k_ne_rs_u(DevProblem P, const double *__r
 #pragma unroll
     for (int e = 0; e < NA; ++e) {
         double v = acc[e];
+        // wave_sum written out: the call changes this kernel's register allocation
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0) wsum[wv][e] = v;
@@ -469,7 +469,7 @@ __global__ void __launch_bounds__(256) k_rs_offdiag(DevProblem P, const double *
 void launch_jacobian_rs(hipStream_t s, const DevProblem &P, const double *ext_pert,
                         const double *step, int solver_type, double *J, int *jcol, int *nloc,
                         const int *stale_param, double *eu, double *ed) {
-    k_jacobian_rs<64><<<nblk_rs(P.M, 64), 64, 0, s>>>(P, ext_pert, step, solver_type, J, jcol,
+    k_jacobian_rs<64><<<nblk(P.M, 64), 64, 0, s>>>(P, ext_pert, step, solver_type, J, jcol,
                                                       nloc, stale_param, eu, ed);
 }
 
@@ -489,7 +489,7 @@ void launch_ne_rs(hipStream_t s, const DevProblem &P, const double *J, const int
 
 void launch_rs_offdiag(hipStream_t s, const DevProblem &P, const SView &V) {
     const long n = (long)P.ncf * 2 * PCMAX * PCMAX;
-    if (n > 0) k_rs_offdiag<<<nblk_rs(n, 256), 256, 0, s>>>(P, P.rs_Aoff, V);
+    if (n > 0) k_rs_offdiag<<<nblk(n, 256), 256, 0, s>>>(P, P.rs_Aoff, V);
 }
 
 }  // namespace mmba

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(256) kchain(double *out, long long *cyc, doubl
         if (ST && lane >= K && lane < 2 * K) {
             double *dst = gst + (threadIdx.x >> 6) * K * K + (lane - K) * K;
 #pragma unroll
-            for (int i = 0; i < K; ++i) bcr_st(dst + i, a[i]);
+            for (int i = 0; i < K; ++i) st_sc1(dst + i, a[i]);
         }
         sink += a[K - 1] + a[3];
     }
