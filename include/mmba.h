@@ -811,7 +811,20 @@ int mmba_plan_kernel_stats(mmba_plan *plan, int enable_timing,
                                      form wherever its grid is resident (the default).  No
                                      value forces the 512-thread form: beyond residency its
                                      workgroups would wait on blocks that are not running */
-#define MMBA_PATH_NUM 30
+#define MMBA_PATH_LOADS_FIRST 30  /* 0: the fused Jacobian pass (k_jac_ne_u) loads its epilogue's
+                                     operands (parameter indices, diag, x, ||f||) after its
+                                     observation loop, the bundle pass (k_ne_bnd_jb) loads them
+                                     parameter by parameter between its stores, and k_schur_obs
+                                     walks bundle -> camera-frame -> variant tables to its
+                                     columns; 1: the fused pass loads them ahead of its loop and
+                                     parks them in LDS (no global load behind the pass's stores)
+                                     and forms its wave sums by vector-unit lane moves instead
+                                     of ds_bpermute (all-fast-bundle plans; the others keep its
+                                     earlier form), the bundle pass loads them with its first
+                                     index loads, and k_schur_obs reads one packed
+                                     per-observation plan word (same operations in the same
+                                     order: same bits).  Default: 1 */
+#define MMBA_PATH_NUM 31
 int mmba_debug_set_path(int key, int value);
 
 /* Test hook (not part of the solver seam): solve S x = r with the device

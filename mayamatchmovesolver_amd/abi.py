@@ -54,7 +54,8 @@ PATH_LENS_SHARED = 26
 PATH_OBJ_CF = 27
 PATH_OBJ_REC = 28
 PATH_PCR_WIDE = 29
-PATH_NUM = 30
+PATH_LOADS_FIRST = 30
+PATH_NUM = 31
 
 FILM_FIT_FILL = 0
 FILM_FIT_HORIZONTAL = 1

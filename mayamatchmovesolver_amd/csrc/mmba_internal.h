@@ -338,6 +338,12 @@ struct DevProblem {
     // is fast and nG == 0)
     const int *obs_bpos;
     double *JB;
+    // what k_schur_obs needs of observation i besides its bundle, one word:
+    // s | pc << 8 | pb << 16 with s the camera-frame's variant count (the
+    // offset of the bundle's columns in the row), pc its block size and pb
+    // the bundle's (plan constants: cf_var_off, cf_pc and bnd_pb of obs_cf[i]
+    // / obs_bnd[i])
+    const int *obs_sp;
     // per camera lens parameter lists (the batched per-frame solve, where
     // the reference solves one frame at a time and no index mixes)
     const int *cam_lpar_off, *cam_lpar;

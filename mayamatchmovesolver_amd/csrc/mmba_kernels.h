@@ -204,10 +204,19 @@ struct NeEpi {
     // enqueued ahead of the host's decision, LmDec)
     const int *gate = nullptr;
     // MMBA_PATH_PROBE = 2: k_jac_ne_u stores, per workgroup (logical
-    // camera-frame), the wall clock at entry, after staging, after its
-    // observations and at exit, and its XCC id
+    // camera-frame), K2_PROBE_N words: the wall clock at entry, after
+    // staging, after its observations and at exit, its XCC id, a spare
+    // word, then the clock behind the wave sums' barrier and at the start of
+    // the epilogue (no stamp inside the observation loop: one there cost
+    // the kernel 0.5 us with the probe off)
     long long *probe = nullptr;
+    // MMBA_PATH_LOADS_FIRST: k_jac_ne_u parks the epilogue's operands in
+    // LDS ahead of its loop and k_ne_bnd_jb loads them with its index loads,
+    // so neither issues a global load behind its stores, and k_jac_ne_u's
+    // wave sums stay off the LDS pipe (same operations, same bits)
+    int loads_first = 0;
 };
+constexpr int K2_PROBE_N = 8;
 // The trial's reduction and LM decision carried by the gated Jacobian launch
 // behind it (MMBA_PATH_TRIAL_RED_FOLD) instead of a k_reduce_multi launch
 // between the two.  Every camera-frame workgroup of k_jac_ne_u reduces the
@@ -253,9 +262,11 @@ void launch_colnorms(hipStream_t s, const DevProblem &P, const double *Acc, cons
 void launch_bundle_factor(hipStream_t s, const DevProblem &P, const double *Abb,
                           const double *Abg, const double *g, const double *diag, double lam,
                           double *Lb, double *tb, double *Wg, int *fail);
+// packed (MMBA_PATH_LOADS_FIRST): the columns' offset and the block widths
+// from P.obs_sp instead of the bundle -> camera-frame -> variant tables
 void launch_schur_obs(hipStream_t s, const DevProblem &P, const double *J, const double *Lb,
                       double *W, const RedSpec *red = nullptr, const double *partial = nullptr,
-                      double *scalar = nullptr, const int *gate = nullptr);
+                      double *scalar = nullptr, const int *gate = nullptr, bool packed = false);
 // rolling shutter with solved bundles: W rows of the virtual observations
 // (Plan::build, PV)
 void launch_schur_obs_rs(hipStream_t s, const DevProblem &PV, int Mr, const int *nloc,

@@ -831,8 +831,8 @@ __device__ __forceinline__ EpiPre epi_preload(const DevProblem &P, const NeEpi &
     return q;
 }
 // epi_param with its loads done (same operations, same bits)
-__device__ __forceinline__ void epi_param_pre(const NeEpi &E, const EpiPre &q, double d, double gp,
-                                              double &zf, double &xn, double &gm) {
+__device__ __forceinline__ double epi_param_pre(const NeEpi &E, const EpiPre &q, double d,
+                                                double gp, double &zf, double &xn, double &gm) {
     const double an = sqrt(d);
     E.acnorm[q.p] = an;
     double dg = q.dg;
@@ -849,6 +849,7 @@ __device__ __forceinline__ void epi_param_pre(const NeEpi &E, const EpiPre &q, d
     if (E.do_gn && an != 0.) {
         if (q.fn != 0.) gm = fmax(gm, fabs((gp / q.fn) / an));
     }
+    return dg;  // diag[p] as stored
 }
 template <int PC>
 __device__ __forceinline__ void epi_params_wave(const DevProblem &P, const NeEpi &E, int cf,
@@ -1202,7 +1203,16 @@ __device__ __forceinline__ LmOut trial_decide(const TrialRed &R, const double *s
     return lm_decide_vals(R.dec, tin);
 }
 
-template <int PC, int NW, bool GEN>
+// LF (MMBA_PATH_LOADS_FIRST): the epilogue's operands -- diag[p], x[p] of the
+// block's parameters and ||f||^2 -- are loaded ahead of the loop, behind the
+// trial's rows, and parked in LDS, so no global load is issued behind the
+// observations' stores (loads and stores share one in-order counter: a load
+// behind them waits for every store's acknowledgement, then once more per
+// dependent level).  diag[p] and x[p] of a camera-frame's parameters are
+// written by launches ahead of this one and by this workgroup's own epilogue
+// only: the early read sees the same values.  The wave sums go through
+// wave_sum_lane0 (no ds_bpermute).  Instantiated for GEN = false only.
+template <int PC, int NW, bool GEN, bool LF>
 __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
     DevProblem P, const double *__restrict__ recs, const double *__restrict__ step,
     int solver_type, double *__restrict__ J, int *__restrict__ jcol, int *__restrict__ nloc,
@@ -1217,6 +1227,7 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
     __shared__ double sSt[PC];
     __shared__ int sHdr[3];  // nv, frame, stale column
     __shared__ double sTr[5];  // R.on: the trial's rows as this workgroup reduced them
+    __shared__ double sDg[LF ? PC : 1], sXv[LF ? PC : 1], sFs[1];  // LF: diag[p], x[p], ||f||^2
     // a Jacobian enqueued ahead of the host's decision runs only when the
     // device's restatement of that decision (lm_decide) let it: read from the
     // gate k_reduce_multi wrote, or (R.on) taken here
@@ -1244,11 +1255,12 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
         return;
     }
     const int cf = xcd_remap((int)blockIdx.x - pad, ncf);
-    long long *pr = (E.probe && threadIdx.x == 0) ? E.probe + 5 * (size_t)cf : nullptr;
+    long long *pr = (E.probe && threadIdx.x == 0) ? E.probe + K2_PROBE_N * (size_t)cf : nullptr;
     const long long t_in = pr ? (long long)wall_clock64() : 0;  // stored once the gate is known open
     const int o0 = P.cf_obs_off[cf], o1 = P.cf_obs_off[cf + 1];
     const bool lmder = solver_type == MMBA_SOLVER_CMINPACK_LMDER;
     const bool solved = P.cf_pc[cf] == PC && own_cf(P, cf);  // sharded: owner's blocks only
+    [[maybe_unused]] int pE = -1;  // LF: the parameter of thread tid < PC
     {
         // the staging's first loads, then (R.on) the loads of the trial's rows
         // and of the decision's slots, then the staging's dependent loads:
@@ -1269,6 +1281,7 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
         const int fr = P.cf_frame[cf];
         if (R.on) trial_rows_issue<NW>(R, tin, TR);
         const double stv = p >= 0 ? step[p] : 1.;
+        pE = p;
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
             const int t = tid + 64 * NW * k;
@@ -1285,10 +1298,32 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
         }
     }
     if (R.on) trial_rows_finish<NW>(R, sTr, TR);
+    // LF: the epilogue's operands, in flight under the barrier and the
+    // decision (behind the trial's rows: the staging holds too many scalars)
+    [[maybe_unused]] double dgv = 0., xvv = 0., fsv = 0.;
+    if constexpr (LF) {
+        // (whether the camera-frame is solved and x is wanted is asked by the
+        // epilogue: the fewer conditions held across the loop, the fewer scalars)
+        if (E.on) {
+            if (pE >= 0) {
+                dgv = E.diag[pE];
+                xvv = E.x[pE];
+            }
+            if (tid == 0 && !R.on && E.fnorm_sq) fsv = *E.fnorm_sq;
+        }
+    }
     __syncthreads();
     // every workgroup takes the decision on its own values: no ticket, no
     // wait; a closed gate returns here, nothing written before it
     if (R.on && trial_decide(R, sTr, tin, TR.dn_dup).go == 0) return;
+    if constexpr (LF) {
+        // parked in LDS (read back by the same threads): no register across the loop
+        if (tid < PC) {
+            sDg[tid] = dgv;
+            sXv[tid] = xvv;
+        }
+        if (tid == 0) sFs[0] = fsv;
+    }
     if (pr) {
         pr[0] = t_in;
         pr[1] = (long long)wall_clock64();
@@ -1332,12 +1367,20 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         double v = acc[e];
-        // wave_sum written out: the call changes this kernel's instruction schedule
+        if constexpr (LF) {
+            // every wave of the CU reduces at this point: the butterfly's
+            // ds_bpermute queue on the one LDS pipe (6 us of the 7.7 us tail
+            // on C4); lane 0's sum through the vector unit, same bits
+            v = wave_sum_lane0(v);
+        } else {
+            // wave_sum written out: the call changes this kernel's instruction schedule
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        }
         if (lane == 0) wsum[wv][e] = v;
     }
     __syncthreads();
+    if (pr) pr[6] = (long long)wall_clock64();
     double *A = &Acc[(size_t)cf * PCMAX * PCMAX];
     for (int e = tid; e < NE; e += 64 * NW) {
         double v = wsum[0][e];
@@ -1352,10 +1395,13 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
             const int c = a + rem;
             A[a * PCMAX + c] = v;
             A[c * PCMAX + a] = v;
+        } else if constexpr (LF) {
+            g[sPv[e - NCC]] = v;
         } else {
             g[P.cf_var_param[P.cf_var_off[cf] + 1 + (e - NCC)]] = v;
         }
     }
+    if (pr) pr[7] = (long long)wall_clock64();
     if (E.on && (tid >> 6) == 0) {
         const int ln = tid & 63;
         double d = 0., gp = 0.;
@@ -1369,11 +1415,24 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
                 gp += wsum[w][NCC + ln];
             }
         }
-        // (loaded here: preloaded before the loop they cost this 232-VGPR
-        // kernel its second wave per SIMD)
         // (R.on: ||f||^2 is the workgroup's own row value, not the slot the
         // extra workgroup is writing)
-        epi_params_wave<PC>(P, E, cf, ln, d, gp, epi_preload<PC>(P, E, cf, ln, R.on != 0, sTr[2]));
+        // (!LF: loaded here -- preloaded before the loop and held in
+        // registers they cost this 232-VGPR kernel its second wave per SIMD)
+        if constexpr (LF) {
+            // epi_preload's values, from the LDS copies made ahead of the loop
+            EpiPre q{-1, 0., 0., 0.};
+            if (ln < PC) {
+                q.p = sPv[ln];
+                q.dg = sDg[ln];
+                if (E.do_xn) q.xv = sXv[ln];
+                if (E.do_gn) q.fn = R.on ? sqrt(sTr[2]) : E.fnorm_sq ? sqrt(sFs[0]) : E.fnorm;
+            }
+            epi_params_wave<PC>(P, E, cf, ln, d, gp, q);
+        } else {
+            epi_params_wave<PC>(P, E, cf, ln, d, gp,
+                                epi_preload<PC>(P, E, cf, ln, R.on != 0, sTr[2]));
+        }
     }
     if (pr) {
         pr[3] = (long long)wall_clock64();
@@ -1388,6 +1447,13 @@ __global__ void __launch_bounds__(64 * NW) k_jac_ne_u(
 // NE_BND_TPB threads per workgroup (C4: 782 workgroups over 256 CUs, so
 // several waves per CU hide the record loads); a bundle's records are loaded
 // four at a time before they are accumulated (C4's bundles have four).
+// LF (MMBA_PATH_LOADS_FIRST): the epilogue's operands (diag, x of the bundle's
+// parameters, ||f||) are loaded with the first index loads, ahead of every
+// store -- through NeEpi's unqualified pointers each of epi_param's loads
+// otherwise waits behind the stores of the parameter before it (and of Abb
+// and g): up to nine serialised round trips in a kernel with under one wave
+// per SIMD.  A bundle's diag / x are written by its own thread only.
+template <bool LF>
 __global__ void __launch_bounds__(NE_BND_TPB) k_ne_bnd_jb(DevProblem P, double *Abb, double *g,
                                                           NeEpi E) {
     __shared__ double red[3][NE_BND_TPB];
@@ -1404,6 +1470,21 @@ __global__ void __launch_bounds__(NE_BND_TPB) k_ne_bnd_jb(DevProblem P, double *
         double gb[PBMAX] = {};
         const int q0 = P.bobs_off[b], q1 = P.bobs_off[b + 1];
         const double *__restrict__ br = &P.brec[(size_t)b * BREC];
+        [[maybe_unused]] EpiPre eq[3] = {{p4.x, 0., 0., 0.}, {p4.y, 0., 0., 0.}, {p4.z, 0., 0., 0.}};
+        if constexpr (LF) {
+            if (E.on) {
+                const double fn =
+                    E.do_gn ? (E.fnorm_sq ? sqrt(*E.fnorm_sq) : E.fnorm) : 0.;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    if (a < pb) {
+                        eq[a].dg = E.diag[eq[a].p];
+                        if (E.do_xn) eq[a].xv = E.x[eq[a].p];
+                    }
+                    eq[a].fn = fn;
+                }
+            }
+        }
         for (int qb = q0; qb < q1; qb += 4) {
             double4 u[4], v[4];
             if (E.jb_recs) {
@@ -1467,9 +1548,15 @@ __global__ void __launch_bounds__(NE_BND_TPB) k_ne_bnd_jb(DevProblem P, double *
             // sharded: every bundle of the shard gets acnorm / diag, only the
             // owned ones enter the rank-summed scalars
             double zo = 0., xo = 0., go = 0.;
-            dd[0] = epi_param(E, p4.x, A[0][0], gb[0], zo, xo, go);
-            if (pb > 1) dd[1] = epi_param(E, p4.y, A[1][1], gb[1], zo, xo, go);
-            if (pb > 2) dd[2] = epi_param(E, p4.z, A[2][2], gb[2], zo, xo, go);
+            if constexpr (LF) {  // epi_param with its loads done
+                dd[0] = epi_param_pre(E, eq[0], A[0][0], gb[0], zo, xo, go);
+                if (pb > 1) dd[1] = epi_param_pre(E, eq[1], A[1][1], gb[1], zo, xo, go);
+                if (pb > 2) dd[2] = epi_param_pre(E, eq[2], A[2][2], gb[2], zo, xo, go);
+            } else {
+                dd[0] = epi_param(E, p4.x, A[0][0], gb[0], zo, xo, go);
+                if (pb > 1) dd[1] = epi_param(E, p4.y, A[1][1], gb[1], zo, xo, go);
+                if (pb > 2) dd[2] = epi_param(E, p4.z, A[2][2], gb[2], zo, xo, go);
+            }
             if (own_bnd(P, b)) {
                 zf = zo;
                 xn = xo;
@@ -2038,7 +2125,12 @@ __global__ void k_bundle_factor(DevProblem P, const double *__restrict__ Abb,
 // gate (enqueued behind the gated Jacobian, Plan::pre_jac_enqueue): runs
 // only when the device's restatement of the host's decision let the
 // Jacobian run.
-template <int PCT>
+// PK (MMBA_PATH_LOADS_FIRST): the bundle columns' offset and the two block
+// widths from the observation's packed plan word P.obs_sp[i], loaded with
+// obs_bnd[i], and Lb[b] issued as soon as b is known: two dependent load
+// levels ahead of the first product instead of five (obs_bnd -> bnd_pb ->
+// obs_cf -> cf_pc / cf_var_off -> J).
+template <int PCT, bool PK>
 __global__ void __launch_bounds__(64) k_schur_obs(DevProblem P, const double *__restrict__ J,
                                                   const double *__restrict__ Lb, double *W,
                                                   int nob, const RedSpec red,
@@ -2057,21 +2149,43 @@ __global__ void __launch_bounds__(64) k_schur_obs(DevProblem P, const double *__
     const int i = i0 + lane;
     const int M = P.M, wst = P.wst;
     double *row = &sw[lane * wst];
+    int b, pb, pck = 0;
+    if constexpr (PK) {
+        b = i < M ? P.obs_bnd[i] : 0;
+        pck = i < M ? P.obs_sp[i] : 0;
+        pb = pck >> 16;
+    }
     for (int k = 0; k < wst; ++k) row[k] = 0.;
-    const int b = i < M ? P.obs_bnd[i] : 0;
-    const int pb = i < M ? P.bnd_pb[b] : 0;
+    if constexpr (!PK) {
+        b = i < M ? P.obs_bnd[i] : 0;
+        pb = i < M ? P.bnd_pb[b] : 0;
+    }
     if (pb > 0) {
-        const int cf = P.obs_cf[i];
-        const int pc = min(min(P.cf_pc[cf], wst / 3), PCT);
-        const int s = P.cf_var_off[cf + 1] - P.cf_var_off[cf] - 1;
+        int pc, s;
+        if constexpr (PK) {
+            pc = min(min((pck >> 8) & 255, wst / 3), PCT);
+            s = pck & 255;
+        } else {
+            const int cf = P.obs_cf[i];
+            pc = min(min(P.cf_pc[cf], wst / 3), PCT);
+            s = P.cf_var_off[cf + 1] - P.cf_var_off[cf] - 1;
+        }
         // every index static (no scratch): bundle columns a < pb, camera rows r < pc
         double bx[3], by[3], L[3][3], il[3];
+        if constexpr (PK) {  // needs b only
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) L[a][c] = Lb[(size_t)b * 9 + a * 3 + c];
+        }
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             bx[a] = a < pb ? J[(size_t)(2 * (s + a)) * M + i] : 0.;
             by[a] = a < pb ? J[(size_t)(2 * (s + a) + 1) * M + i] : 0.;
+            if constexpr (!PK) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) L[a][c] = Lb[(size_t)b * 9 + a * 3 + c];
+                for (int c = 0; c < 3; ++c) L[a][c] = Lb[(size_t)b * 9 + a * 3 + c];
+            }
         }
 #pragma unroll
         for (int a = 0; a < 3; ++a) il[a] = a < pb ? 1.0 / L[a][a] : 0.;
@@ -3860,19 +3974,22 @@ void launch_jac_ne(hipStream_t s, const DevProblem &P, const double *recs, const
     // segment: 2 waves 41.7 us, 4 waves 34.6 us, 8 waves 45.7 us)
     const long long per = (P.M + P.ncf - 1) / P.ncf;
     int nw = per > 1024 ? 8 : (per > 256 ? 4 : 2);
-#define MMBA_JN(PC, NW, GEN)                                                                  \
-    k_jac_ne_u<PC, NW, GEN><<<grid, 64 * NW, 0, s>>>(P, recs, step, solver_type, J, jcol, nloc, \
-                                                       stale_param, eu, ed, Acc, g, E, R)
-#define MMBA_JN_NW(PC, GEN)                                         \
+#define MMBA_JN_LF(PC, NW, GEN, LF)                                                           \
+    k_jac_ne_u<PC, NW, GEN, LF><<<grid, 64 * NW, 0, s>>>(P, recs, step, solver_type, J, jcol,  \
+                                                           nloc, stale_param, eu, ed, Acc, g, E, R)
+#define MMBA_JN_NW(PC, GEN, LF)                                     \
     do {                                                            \
-        if (nw == 8) MMBA_JN(PC, 8, GEN);                           \
-        else if (nw == 4) MMBA_JN(PC, 4, GEN);                      \
-        else MMBA_JN(PC, 2, GEN);                                   \
+        if (nw == 8) MMBA_JN_LF(PC, 8, GEN, LF);                    \
+        else if (nw == 4) MMBA_JN_LF(PC, 4, GEN, LF);               \
+        else MMBA_JN_LF(PC, 2, GEN, LF);                            \
     } while (0)
+    // (the GEN instances keep the epilogue's loads behind the loop: parked
+    // ahead of it, their four- and eight-wave forms spill scalars)
 #define MMBA_JN_PC(PC)                                              \
     do {                                                            \
-        if (P.all_bnd_fast) MMBA_JN_NW(PC, false);                  \
-        else MMBA_JN_NW(PC, true);                                  \
+        if (!P.all_bnd_fast) MMBA_JN_NW(PC, true, false);           \
+        else if (E.loads_first) MMBA_JN_NW(PC, false, true);        \
+        else MMBA_JN_NW(PC, false, false);                          \
     } while (0)
     if (P.pc_uniform == 6)
         MMBA_JN_PC(6);
@@ -3880,7 +3997,7 @@ void launch_jac_ne(hipStream_t s, const DevProblem &P, const double *recs, const
         MMBA_JN_PC(7);
 #undef MMBA_JN_PC
 #undef MMBA_JN_NW
-#undef MMBA_JN
+#undef MMBA_JN_LF
 }
 // [ZERO, XN2, gnorm_0 .. gnorm_{n-1}] after the sum all-reduce -> the
 // ZERO / XN2 / GNORM slots (gnorm = max over ranks)
@@ -4271,8 +4388,10 @@ bool launch_ne(hipStream_t s, const DevProblem &P, const double *J, const int *j
     // host blocks, and the coupling blocks
     if (P.ls_ng > 0) launch_ne_lens_shared(s, P, J, jcol, nloc, f, Acc, Acg, g);
     if (P.nbs > 0) {
-        if (P.JB)  // every solved bundle fast and no global parameters
-            k_ne_bnd_jb<<<nblk(P.nB, NE_BND_TPB), NE_BND_TPB, 0, s>>>(P, Abb, g, E);
+        if (P.JB && E.loads_first)  // every solved bundle fast and no global parameters
+            k_ne_bnd_jb<true><<<nblk(P.nB, NE_BND_TPB), NE_BND_TPB, 0, s>>>(P, Abb, g, E);
+        else if (P.JB)
+            k_ne_bnd_jb<false><<<nblk(P.nB, NE_BND_TPB), NE_BND_TPB, 0, s>>>(P, Abb, g, E);
         else
             k_ne_bnd<<<nblk(P.nB, 64), 64, 0, s>>>(P, J, jcol, nloc, f, Abb, Abg, g);
     }
@@ -4307,15 +4426,19 @@ void launch_bundle_factor(hipStream_t s, const DevProblem &P, const double *Abb,
 }
 void launch_schur_obs(hipStream_t s, const DevProblem &P, const double *J, const double *Lb,
                       double *W, const RedSpec *red, const double *partial, double *scalar,
-                      const int *gate) {
+                      const int *gate, bool packed) {
     const int nob = nblk(P.M, 64), nr = red ? red->nrows : 0;
     if (nob + nr > 0) {
-        if (P.wst / 3 <= 8)
-            k_schur_obs<8><<<nob + nr, 64, sizeof(double) * 64 * P.wst, s>>>(
-                P, J, Lb, W, nob, red ? *red : RedSpec{}, partial, scalar, gate);
-        else
-            k_schur_obs<PCMAX><<<nob + nr, 64, sizeof(double) * 64 * P.wst, s>>>(
-                P, J, Lb, W, nob, red ? *red : RedSpec{}, partial, scalar, gate);
+#define MMBA_SO(PCT, PK)                                                    \
+    k_schur_obs<PCT, PK><<<nob + nr, 64, sizeof(double) * 64 * P.wst, s>>>( \
+        P, J, Lb, W, nob, red ? *red : RedSpec{}, partial, scalar, gate)
+        const bool pk = packed && P.obs_sp != nullptr;
+        if (P.wst / 3 <= 8) {
+            if (pk) MMBA_SO(8, true); else MMBA_SO(8, false);
+        } else {
+            if (pk) MMBA_SO(PCMAX, true); else MMBA_SO(PCMAX, false);
+        }
+#undef MMBA_SO
     }
 }
 void launch_schur_obs_rs(hipStream_t s, const DevProblem &PV, int Mr, const int *nloc,

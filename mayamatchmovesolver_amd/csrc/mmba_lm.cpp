@@ -299,6 +299,11 @@ bool Plan::trial_red_fold() const {
     return pin < 0 ? kTrialRedFold : pin != 0;
 }
 
+bool Plan::loads_first() const {
+    const int pin = path_choice(MMBA_PATH_LOADS_FIRST);
+    return pin < 0 ? kLoadsFirst : pin != 0;
+}
+
 // The fused epilogue of the Jacobian at dx: lmder's bookkeeping rides in the
 // normal-equation kernels, which leave one partial per quantity and block.
 NeEpi Plan::fused_epi(const double *dx, const JacLM &lm) const {
@@ -318,6 +323,7 @@ NeEpi Plan::fused_epi(const double *dx, const JacLM &lm) const {
     e.cf_base = 0;
     e.bnd_base = ncf;
     e.probe = d_k2probe;
+    e.loads_first = loads_first() ? 1 : 0;
     return e;
 }
 
@@ -424,7 +430,7 @@ void Plan::pre_jac_enqueue(const double *dx, double *eu, double *ed, const Trial
     if (fl.pre_bnd_pending && lb0 && !rs_bnd && red_defer_ok() &&
         path_choice(MMBA_PATH_PRE_SCHUR) == 1) {
         const RedSpec rs = epi_rows(pw, epi_ncol(*this), epi.do_xn, epi.do_gn);
-        launch_schur_obs(s, P, d_J, d_Lb, d_W, &rs, d_partial, d_scalar, d_gate);
+        launch_schur_obs(s, P, d_J, d_Lb, d_W, &rs, d_partial, d_scalar, d_gate, loads_first());
         fl.pre_sobs_pending = true;
     }
     fl.pre_jac_x = dx;
@@ -488,6 +494,7 @@ void Plan::jac(const double *dx, const JacLM *lm) {
     const bool fuse = lm && ne_epilogue_fusable(P) && nrows == 0 && !b15;
     NeEpi epi;
     epi.probe = d_k2probe;
+    epi.loads_first = loads_first() ? 1 : 0;
     fl.lb0_valid = false;
     if (fuse) {
         epi = fused_epi(dx, *lm);
@@ -754,7 +761,7 @@ void Plan::solve_damped_enqueue(double lam, int dnorm_slot, bool defer, bool dno
             launch_schur_obs_rs(s, PV, M, d_nloc, d_vobs, d_vcoff, d_J, d_Lb, d_W);
         else if (!ahead) {
             launch_schur_obs(s, P, d_J, d_Lb, d_W, fl.pend_red ? &pend_rs : nullptr, d_partial,
-                             d_scalar);
+                             d_scalar, nullptr, loads_first());
             fl.pend_red = false;
         }
     }

@@ -30,19 +30,22 @@ Plan::~Plan() {
     if (d_k2probe) {
         // the last k_jac_ne_u launch: per workgroup entry / staged / observations
         // done / exit (10-ns ticks), summarised in microseconds
-        std::vector<long long> t(5 * (size_t)ncf);
+        // the tail in its parts: the wave sums up to their barrier, the
+        // Acc / g stores up to the epilogue, the epilogue
+        constexpr int N = K2_PROBE_N;
+        std::vector<long long> t(N * (size_t)ncf);
         if (hipMemcpy(t.data(), d_k2probe, sizeof(long long) * t.size(), hipMemcpyDeviceToHost) ==
             hipSuccess) {
             long long t0 = LLONG_MAX, tend = 0;
             for (int c = 0; c < ncf; ++c)
-                if (t[5 * c]) {
-                    t0 = std::min(t0, t[5 * c]);
-                    tend = std::max(tend, t[5 * c + 3]);
+                if (t[N * c]) {
+                    t0 = std::min(t0, t[N * c]);
+                    tend = std::max(tend, t[N * c + 3]);
                 }
-            std::vector<double> st, stg, obs, tail, tot;
+            std::vector<double> st, stg, obs, tail, tot, sums, stor, epi;
             int per_xcc[16] = {};
             for (int c = 0; c < ncf; ++c) {
-                const long long *q = &t[5 * c];
+                const long long *q = &t[N * c];
                 if (!q[0]) continue;
                 st.push_back((q[0] - t0) / 100.);
                 stg.push_back((q[1] - q[0]) / 100.);
@@ -50,6 +53,11 @@ Plan::~Plan() {
                 tail.push_back((q[3] - q[2]) / 100.);
                 tot.push_back((q[3] - q[0]) / 100.);
                 per_xcc[q[4] & 15]++;
+                if (q[6] && q[7]) {
+                    sums.push_back((q[6] - q[2]) / 100.);
+                    stor.push_back((q[7] - q[6]) / 100.);
+                    epi.push_back((q[3] - q[7]) / 100.);
+                }
             }
             auto pct = [](std::vector<double> v, double p) {
                 if (v.empty()) return 0.;
@@ -64,7 +72,10 @@ Plan::~Plan() {
                          pct(obs, 1), pct(tail, 0), pct(tail, .5), pct(tail, 1), pct(tot, 0),
                          pct(tot, .5), pct(tot, 1));
             for (int x = 0; x < 8; ++x) std::fprintf(stderr, " %d", per_xcc[x]);
-            std::fprintf(stderr, "\n");
+            std::fprintf(stderr, "; tail: sums %.2f/%.2f/%.2f stores %.2f/%.2f/%.2f "
+                                 "epilogue %.2f/%.2f/%.2f\n",
+                         pct(sums, 0), pct(sums, .5), pct(sums, 1), pct(stor, 0), pct(stor, .5),
+                         pct(stor, 1), pct(epi, 0), pct(epi, .5), pct(epi, 1));
         }
     }
     if (d_probe && bs.use_bcr && bs.bcr.fflags && bs.bcr.nblk >= 2) {
@@ -1518,6 +1529,18 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         }
         d_bobs_rp = upload(rp);
     }
+    {
+        // k_schur_obs's per-observation word (MMBA_PATH_LOADS_FIRST)
+        std::vector<int> sp(M);
+        bool fits = true;  // (a camera-frame with more variants keeps the table walk)
+        for (int i = 0; i < M; ++i) {
+            const int cf = d_cf[i];
+            const int sv = cf_var_off[cf + 1] - cf_var_off[cf] - 1;
+            fits = fits && sv >= 0 && sv < 256;
+            sp[i] = sv | (cf_pc[cf] << 8) | (bnd_pb[d_bnd[i]] << 16);
+        }
+        D.obs_sp = fits ? upload(sp) : nullptr;
+    }
     D.cam_lpar_off = upload(cam_lpar_off);
     {
         bool any_inst = false;
@@ -1893,8 +1916,9 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
         }
     if (band) setup_band();
     if (path_choice(MMBA_PATH_PROBE) == 2) {  // k_jac_ne_u workgroup timeline
-        d_k2probe = dalloc<long long>(5 * (size_t)std::max(ncf, 1));
-        MMBA_HIP(hipMemsetAsync(d_k2probe, 0, 5 * (size_t)std::max(ncf, 1) * sizeof(long long), s));
+        const size_t np = K2_PROBE_N * (size_t)std::max(ncf, 1);
+        d_k2probe = dalloc<long long>(np);
+        MMBA_HIP(hipMemsetAsync(d_k2probe, 0, np * sizeof(long long), s));
     }
     if (band && path_choice(MMBA_PATH_PROBE) == 1) {
         const size_t np = 8 + 4 * ((size_t)std::max(nR, 1) + 64);  // + the dataflow trace

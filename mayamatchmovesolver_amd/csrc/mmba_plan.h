@@ -530,6 +530,9 @@ struct Plan {
     // Unpinned choice of MMBA_PATH_TRIAL_RED_FOLD
     static constexpr bool kTrialRedFold = true;
     bool trial_red_fold() const;
+    // Unpinned choice of MMBA_PATH_LOADS_FIRST
+    static constexpr bool kLoadsFirst = true;
+    bool loads_first() const;
     void stage_slots();
     RedSpec pend_rs{};  // the rows of InFlight::pend_red
     bool red_defer_ok() const;

@@ -85,6 +85,40 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
 }
+// wave_sum's value of lane 0 through the vector unit's own lane moves
+// (v_permlane32_swap, v_permlane16_swap, DPP row / quad moves) instead of
+// ds_bpermute: lane l adds lane l + 32, then l + 16, then its xor-8 partner,
+// l + 4, and its xor-2 and xor-1 partners.  In lane 0 every step adds the same
+// two subtree sums as the xor butterfly does (a + b == b + a bit for bit), so
+// lane 0 holds wave_sum's bits; the OTHER LANES DO NOT hold the wave's sum.
+// For kernels whose waves all reduce at once: the butterfly's 12 ds_bpermute
+// per double share the CU's one LDS pipe with every other wave on it.
+template <int CTRL>
+__device__ __forceinline__ double wave_dpp_mov(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_sum_lane0(double v) {
+    {  // lanes 0..31 <- lanes 32..63
+        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        v += __hiloint2double((int)b[1], (int)a[1]);
+    }
+    {  // rows 0, 2 <- rows 1, 3
+        const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
+        const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        v += __hiloint2double((int)b[1], (int)a[1]);
+    }
+    v += wave_dpp_mov<0x128>(v);  // row_ror:8 (lane ^ 8 within the row)
+    v += wave_dpp_mov<0x104>(v);  // row_shl:4 (lane + 4)
+    v += wave_dpp_mov<0x4e>(v);   // quad_perm [2, 3, 0, 1] (lane ^ 2)
+    v += wave_dpp_mov<0xb1>(v);   // quad_perm [1, 0, 3, 2] (lane ^ 1)
+    return v;
+}
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
