@@ -618,9 +618,43 @@ int mmba_solve_per_frame(mmba_context *ctx, const mmba_problem *prob,
  * launch).  Same semantics as the batched path of mmba_solve_per_frame;
  * results[num_frames].  MMBA_ERR_UNSUPPORTED (mmba_last_error says why)
  * when the plan's parameters do not split into independent frames -- use
- * mmba_solve_per_frame then. */
+ * mmba_solve_per_frame then.
+ *   Object tracking (an animated transform above bundles, six pose curves
+ * solved per frame): the frames are independent where the plan holds each
+ * object-frame parameter in the block of the camera-frame that reads it.  A
+ * plan of mmba_plan_create_per_frame does so at any frame count; a plan of
+ * mmba_plan_create only above the 48-global cap, and below it this entry
+ * returns MMBA_ERR_UNSUPPORTED with a message that names
+ * mmba_plan_create_per_frame.  Such frames run the object form of the launch
+ * (mmba_batch_obj.hip: up to 32 object record slots per frame -- one per
+ * moving bundle parent seen at the frame and one per parameter of the frame
+ * that moves it).  Still refused, each with its cause: an object read by
+ * several cameras at one frame, a frame beyond the slot capacity, static
+ * parameters (solved bundles), MMBA_PATH_OBJ_CF = 0, and whatever keeps the
+ * object-frame parameters global (central differences, robust loss, rolling
+ * shutter). */
 int mmba_plan_solve_per_frame(mmba_plan *plan, double *x_inout, mmba_result *results,
                               const mmba_callbacks *cb);
+
+/* The whole-problem plan the way per-frame mode needs it (additive:
+ * MMBA_ABI_VERSION stays 12): plain lens instances -- the reference runs one
+ * solveFrames per frame, so no lens index mixes -- and every
+ * object-frame parameter in its reading camera-frame's block wherever the
+ * plan is eligible, at any frame count (what MMBA_PATH_OBJ_CF = 1 pins for
+ * mmba_plan_create; MMBA_PATH_OBJ_CF = 0 still wins).  One device only
+ * (MMBA_ERR_INVALID on a context of several).  The plan serves
+ * mmba_plan_solve_per_frame, mmba_plan_set_attr_values,
+ * mmba_plan_param_layout, mmba_plan_reproject and mmba_plan_destroy;
+ * mmba_plan_solve, _measure, _jacobian and mmba_debug_damped_step return
+ * MMBA_ERR_INVALID on it (its lens instances are not the whole shot's).
+ * mmba_solve_per_frame builds its whole-problem attempt through this. */
+int mmba_plan_create_per_frame(mmba_context *ctx, const mmba_problem *prob,
+                               const mmba_options *opt, mmba_plan **plan);
+
+/* Test hook: k_batch_lm launches this process has enqueued so far (one per
+ * mmba_plan_solve_per_frame call that reached the kernel; the one-plan-per-
+ * frame fallback adds none). */
+long long mmba_debug_batch_launches(void);
 
 /* One-shot convenience: plan_create + plan_solve + plan_destroy. */
 int mmba_solve(mmba_context *ctx, const mmba_problem *prob,

@@ -361,7 +361,9 @@ bool solve_frames_mmba_per_frame(SolverOptions &solverOptions, std::vector<doubl
     // every frame's solveFrames measures its own initial error and writes
     // back only when it got better (adjust_base.cpp:1080-1103, 1227-1244)
     const mmba_options o = options_of(options_of_maya(solverOptions), /*per_frame=*/true);
-    mmba_plan *plan = s.plan_for(scene, prob, o);
+    // the per-frame plan: plain lens instances, an object's per-frame pose
+    // parameters in the camera-frame blocks (one launch for every frame)
+    mmba_plan *plan = s.plan_for(scene, prob, o, /*per_frame=*/true);
     if (!plan) return false;
     const mmba_callbacks cb = callbacks_of(userData);
     std::vector<mmba_result> res(static_cast<size_t>(prob.num_frames));

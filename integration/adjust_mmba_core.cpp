@@ -544,8 +544,9 @@ bool Shim::ready() {
 }
 
 mmba_plan *Shim::plan_for(const FlatScene &scene, const mmba_problem &prob,
-                          const mmba_options &o) {
+                          const mmba_options &o, bool per_frame) {
     std::vector<uint8_t> key = scene.plan_key(o);
+    key.push_back(per_frame ? 1 : 0);  // the two constructors build different plans
     for (auto it = plans_.begin(); it != plans_.end(); ++it) {
         if (it->key != key) continue;
         if (mmba_plan_set_attr_values(it->plan, prob.attr_values) != MMBA_OK) return nullptr;
@@ -553,7 +554,9 @@ mmba_plan *Shim::plan_for(const FlatScene &scene, const mmba_problem &prob,
         return plans_.front().plan;
     }
     mmba_plan *plan = nullptr;
-    if (mmba_plan_create(ctx_, &prob, &o, &plan) != MMBA_OK) return nullptr;
+    const int rc = per_frame ? mmba_plan_create_per_frame(ctx_, &prob, &o, &plan)
+                             : mmba_plan_create(ctx_, &prob, &o, &plan);
+    if (rc != MMBA_OK) return nullptr;
     plans_.push_front(Entry{std::move(key), plan});
     if (plans_.size() > kMaxPlans) {
         mmba_plan_destroy(plans_.back().plan);

@@ -197,7 +197,10 @@ class Shim {
     ~Shim() { release(); }
     bool ready();              // false: no gfx950 device (the caller runs cminpack)
     const std::string &why() const { return why_; }
-    mmba_plan *plan_for(const FlatScene &scene, const mmba_problem &prob, const mmba_options &o);
+    // per_frame: the plan of per-frame mode (mmba_plan_create_per_frame), for
+    // mmba_plan_solve_per_frame only; cached apart from the whole-shot plan
+    mmba_plan *plan_for(const FlatScene &scene, const mmba_problem &prob, const mmba_options &o,
+                        bool per_frame = false);
     void release();
     size_t cached_plans() const { return plans_.size(); }
 

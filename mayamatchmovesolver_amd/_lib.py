@@ -75,6 +75,10 @@ def lib():
         L.mmba_plan_create.restype = C.c_int
         L.mmba_plan_create.argtypes = [C.c_void_p, C.POINTER(abi.MmbaProblem),
                                        C.POINTER(abi.MmbaOptions), C.POINTER(C.c_void_p)]
+        L.mmba_plan_create_per_frame.restype = C.c_int
+        L.mmba_plan_create_per_frame.argtypes = L.mmba_plan_create.argtypes
+        L.mmba_debug_batch_launches.restype = C.c_longlong
+        L.mmba_debug_batch_launches.argtypes = []
         L.mmba_plan_destroy.restype = None
         L.mmba_plan_destroy.argtypes = [C.c_void_p]
         L.mmba_plan_measure.restype = C.c_int

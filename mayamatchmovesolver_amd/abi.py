@@ -306,6 +306,8 @@ EXPORTED_SYMBOLS = [
     "mmba_plan_outputs",
     "mmba_plan_error_metrics",
     "mmba_plan_param_layout",
+    "mmba_plan_create_per_frame",
+    "mmba_debug_batch_launches",
     "mmba_solve",
     "mmba_plan_kernel_stats",
     "mmba_debug_set_path",

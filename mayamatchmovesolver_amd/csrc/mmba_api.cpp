@@ -304,11 +304,23 @@ int mmba_plan_create_sharded(mmba_context *ctx, const mmba_problem *prob,
     return MMBA_OK;
 }
 
+// A plan of mmba_plan_create_per_frame holds the lens instances of one-frame
+// solves, not the whole shot's: the whole-shot compute entries refuse it.
+static bool refuse_per_frame_plan(const mmba_plan *plan, const char *entry) {
+    if (plan->group || !plan->impl.per_frame_plan) return false;
+    set_error(std::string("invalid: ") + entry + " on a per-frame plan "
+              "(mmba_plan_create_per_frame): its lens instances are those of one-frame solves; "
+              "it serves mmba_plan_solve_per_frame, _set_attr_values, _param_layout and "
+              "_reproject");
+    return true;
+}
+
 void mmba_plan_destroy(mmba_plan *plan) { delete plan; }
 
 int mmba_plan_measure(mmba_plan *plan, const double *x, double *fvec_out, double *err_user_out,
                       double *err_dist_out, double *avg_min_max_out) {
     if (!plan) return MMBA_ERR_INVALID;
+    if (refuse_per_frame_plan(plan, "mmba_plan_measure")) return MMBA_ERR_INVALID;
     if (plan->group)
         return group_plan_measure(plan, x, fvec_out, err_user_out, err_dist_out, avg_min_max_out);
     MMBA_GUARD({
@@ -334,6 +346,7 @@ int mmba_plan_reproject(mmba_plan *plan, const double *x, double *point_xy_out,
 
 int mmba_plan_jacobian(mmba_plan *plan, const double *x, double *fjac) {
     if (!plan || !x || !fjac) return MMBA_ERR_INVALID;
+    if (refuse_per_frame_plan(plan, "mmba_plan_jacobian")) return MMBA_ERR_INVALID;
     if (plan->group) return group_plan_jacobian(plan, x, fjac);
     MMBA_GUARD({
         MMBA_HIP(hipSetDevice(plan->impl.ctx->device));
@@ -346,6 +359,7 @@ int mmba_plan_solve(mmba_plan *plan, double *x_inout, double *fvec_out, double *
                     double *err_dist_out, mmba_result *res, const mmba_callbacks *cb,
                     mmba_trace *trace) {
     if (!plan || !x_inout) return MMBA_ERR_INVALID;
+    if (refuse_per_frame_plan(plan, "mmba_plan_solve")) return MMBA_ERR_INVALID;
     if (plan->group)
         return group_plan_solve(plan, x_inout, fvec_out, err_user_out, err_dist_out, res, cb,
                                 trace);
@@ -571,6 +585,7 @@ int mmba_debug_reduced_residual(mmba_plan *plan, const double *x, double lam, do
 int mmba_debug_damped_step(mmba_plan *plan, const double *x, double lam, double *step_out,
                            double *g_out, double *diag_out, double *fjac_out) {
     if (!plan || !x || !(lam >= 0.)) return MMBA_ERR_INVALID;
+    if (refuse_per_frame_plan(plan, "mmba_debug_damped_step")) return MMBA_ERR_INVALID;
     if (plan->group)
         return group_debug_damped_step(plan, x, lam, step_out, g_out, diag_out, fjac_out);
     MMBA_GUARD({

@@ -165,6 +165,12 @@ struct BdDev {
 // cf_roff of its first camera-frame (fr_par[fr_par_off[f] + k] = parameter).
 constexpr int BATCH_CFMAX = 8;   // camera-frames per frame
 constexpr int BATCH_NFMAX = 32;  // parameters per frame
+// Object record slots per frame in the object form (the workgroup's LDS: 32
+// x ORECSZ doubles = 3 KiB): a base slot per moving bundle parent seen at the
+// frame and a variant slot per parameter of the frame that moves it.  Two
+// objects with all twelve parameters moving both (2 + 24), or an object
+// under an animated parent with bundles of its own (2 + 6), fit.
+constexpr int BATCH_OSLOTS = 32;
 struct BatchOut {
     double fnorm, init_avg, avg, mn, mx, rms;
     int info, nfev, njev, func_evals, jac_evals, interrupted, better, failed;
@@ -434,6 +440,20 @@ struct ObjRecDev {
     double *rec = nullptr;
 };
 struct NoObjRec {};  // the argument of the instantiations that read no record
+
+// Object records of the batched per-frame solve (mmba_batch_obj.hip), built
+// by Plan::build beside fr_par and independent of ObjRecDev (the workgroup
+// builds its frame's records itself, in LDS).  Frame f owns slots
+// [fr_slot_off[f], fr_slot_off[f + 1]) (at most BATCH_OSLOTS), its base slots
+// first; local slot numbers count from the frame's first.  slot_tf: the
+// bundle-parent transform; slot_k: the frame's local parameter whose
+// perturbed value the slot holds (-1: a base slot); slot_set: the local
+// number of the slot's base slot; obs_set[i]: the local base slot of
+// observation i's bundle parent (-1: the bundle record or the chain walk).
+struct BatchObjDev {
+    const int *fr_slot_off = nullptr, *slot_tf = nullptr, *slot_k = nullptr, *slot_set = nullptr;
+    const int *obs_set = nullptr;
+};
 
 __device__ __forceinline__ size_t widx(const DevProblem &P, int k, int i) {
     return (size_t)i * P.wst + k;

@@ -453,8 +453,13 @@ void launch_unpermute(hipStream_t s, int M, const int *ref_of_dev, const int *ob
 void launch_fold_ranks(hipStream_t s, const double *t, int nranks, double *out, int do_xn,
                        int do_gn);
 
-// Per-frame solve mode, one workgroup per frame (mmba_batch.hip).
-void launch_batch_lm(hipStream_t s, const DevProblem &P, const BatchArgs &B, int nf_max);
+// Per-frame solve mode, one workgroup per frame (mmba_batch.hip).  O: the
+// plan's per-frame object tables where some frame's block holds an
+// object-frame parameter (the object form, mmba_batch_obj.hip), else nullptr.
+void launch_batch_lm(hipStream_t s, const DevProblem &P, const BatchArgs &B, int nf_max,
+                     const BatchObjDev *O = nullptr);
+void launch_batch_lm_obj(hipStream_t s, const DevProblem &P, const BatchArgs &B, int nf_max,
+                         const BatchObjDev &O);
 
 // mmba_gemm.hip: C = beta C + alpha A B^T (fp64 MFMA; tri: lower triangle,
 // A == B, M == N); column-major, K a multiple of 16.

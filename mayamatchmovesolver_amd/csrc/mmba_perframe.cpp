@@ -30,6 +30,9 @@
 
 namespace mmba {
 
+// k_batch_lm launches enqueued by this process (mmba_debug_batch_launches)
+static std::atomic<long long> g_batch_launches{0};
+
 // Every frame's solve in one launch (mmba_batch.hip).  The interrupt
 // callback is polled on this (the calling) thread while the launch runs; a
 // request reaches the frames through a host-mapped flag they read at the
@@ -81,8 +84,9 @@ int Plan::solve_frames(double *x_inout, mmba_result *results, const mmba_callbac
     B.xtol = opt.eps2;
     B.gtol = opt.eps3;
     B.initial_error_avg = opt.initial_error_avg;
-    launch_batch_lm(s, P, B, batch_nfmax);
+    launch_batch_lm(s, P, B, batch_nfmax, batch_obj ? &bobj : nullptr);
     MMBA_HIP(hipGetLastError());
+    if (B.nf > 0) g_batch_launches.fetch_add(1, std::memory_order_relaxed);
     if (polls) {
         hipError_t q;
         while ((q = hipStreamQuery(s)) == hipErrorNotReady) {
@@ -152,6 +156,14 @@ struct LensPlain {
     bool prev;
     LensPlain() : prev(mmba::t_lens_plain) { mmba::t_lens_plain = true; }
     ~LensPlain() { mmba::t_lens_plain = prev; }
+};
+// The whole-problem plan of per-frame mode (mmba_plan_create_per_frame) also
+// takes object-frame parameters into the camera-frame blocks at any frame
+// count: as globals they would chain the frames.
+struct ObjInBlocks {
+    bool prev;
+    ObjInBlocks() : prev(mmba::t_obj_cf) { mmba::t_obj_cf = true; }
+    ~ObjInBlocks() { mmba::t_obj_cf = prev; }
 };
 
 
@@ -224,6 +236,25 @@ int solve_frame(mmba_context *ctx, FrameProblem &fp, const mmba_options *opt, do
 
 }  // namespace
 
+extern "C" long long mmba_debug_batch_launches(void) {
+    return mmba::g_batch_launches.load(std::memory_order_relaxed);
+}
+
+extern "C" int mmba_plan_create_per_frame(mmba_context *ctx, const mmba_problem *prob,
+                                          const mmba_options *opt, mmba_plan **plan) {
+    if (!ctx || !prob || !opt || !plan) return MMBA_ERR_INVALID;
+    *plan = nullptr;
+    if (ctx->shards.size() > 1) {
+        mmba::set_error("invalid: a per-frame plan is built on one device");
+        return MMBA_ERR_INVALID;
+    }
+    LensPlain plain_lenses;
+    ObjInBlocks obj_in_blocks;
+    const int rc = mmba_plan_create(ctx, prob, opt, plan);
+    if (rc == MMBA_OK) (*plan)->impl.per_frame_plan = true;
+    return rc;
+}
+
 extern "C" int mmba_solve_per_frame(mmba_context *ctx, const mmba_problem *prob,
                                     const mmba_options *opt, double *x_inout,
                                     mmba_result *results, int32_t max_concurrency,
@@ -249,8 +280,7 @@ extern "C" int mmba_solve_per_frame(mmba_context *ctx, const mmba_problem *prob,
             // (MMBA_PATH_PERFRAME_BATCH = 0: the per-frame plans below)
             if (mmba::path_choice(MMBA_PATH_PERFRAME_BATCH) != 0) {
                 mmba_plan *plan = nullptr;
-                LensPlain plain_lenses;
-                if (mmba_plan_create(ctx, prob, opt, &plan) == MMBA_OK) {
+                if (mmba_plan_create_per_frame(ctx, prob, opt, &plan) == MMBA_OK) {
                     int rc = MMBA_ERR_UNSUPPORTED;
                     if (plan->impl.batch_ok) rc = mmba_plan_solve_per_frame(plan, x_inout, results, cb);
                     mmba_plan_destroy(plan);

@@ -181,6 +181,7 @@ void shard_layout(int F, int M, const int32_t *obs_frame, const int32_t *obs_bnd
 }
 
 thread_local bool t_lens_plain = false;
+thread_local bool t_obj_cf = false;
 
 // Lens instances (mmba.h ABI 7; oracle/refcpu.c b3_build
 // is the checker's restatement).  The reference clones every lens model once
@@ -716,7 +717,7 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     // the forms taken so far first; the object form and the shared form
     // where they leave more than NGMAX globals, or where they are pinned on
     int ng_plain = classify(false);
-    if (has_obj && !obj_off && (obj_pin == 1 || ng_plain > NGMAX)) {
+    if (has_obj && !obj_off && (obj_pin == 1 || t_obj_cf || ng_plain > NGMAX)) {
         obj_form = true;
         ng_plain = classify(false);
     }
@@ -2048,13 +2049,33 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     batch_ok = false;
     {
         const char *why = nullptr;
+        // an object-frame parameter left global names what kept it there
+        std::string why_obj;
+        for (int p = 0; p < n && !why; ++p)
+            if (p_class[p] == PC_G && obj_cam[p] != -3) {
+                if (obj_off)
+                    why_obj = std::string("animated transforms above bundles stay global "
+                                          "parameters: ") + obj_off;
+                else if (!obj_form)
+                    why_obj = "animated transforms above bundles are global parameters of this "
+                              "plan (at most " + std::to_string(NGMAX) + " of them): build the "
+                              "plan with mmba_plan_create_per_frame";
+                else if (obj_cam[p] == -1)
+                    why_obj = "an animated transform above bundles seen by several cameras at "
+                              "one frame stays a global parameter per frame";
+                else
+                    why_obj = "an animated transform above bundles at a frame without a "
+                              "camera-frame stays a global parameter";
+                why = why_obj.c_str();
+            }
         for (int p = 0; p < n && !why; ++p)
             if (p_class[p] != PC_CF) why = "a static or shared parameter chains the frames";
         if (!why && nranks != 1) why = "sharded plan";
         for (int p = 0; p < n && !why; ++p)
             if (p_lens[p]) why = "a lens coefficient in a camera-frame block";
-        for (int p = 0; p < n && !why; ++p)
-            if (p_obj[p]) why = "an object transform parameter in a camera-frame block";
+        batch_obj = false;
+        for (int p = 0; p < n; ++p)
+            if (p_obj[p]) batch_obj = true;
         if (!why && nrows > 0) why = "attribute stiffness / smoothness rows";
         if (!why && rs_on) why = "rolling shutter";
         if (!why && (central || opt.robust_loss)) why = "central differences / robust loss";
@@ -2094,10 +2115,70 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
                 nfmax = std::max(nfmax, nl);
             }
         }
+        // the object form's record slots (BatchObjDev): per solved frame the
+        // moving bundle parents its rows hang under -- the rule of the object
+        // records above, whether or not that table was built -- base slots
+        // first, then a variant per parameter of the frame in a parent's chain
+        std::vector<int> fr_slot_off(F + 1, 0), slot_tf, slot_k, slot_set, obs_bset(M, -1);
+        if (!why && batch_obj) {
+            std::vector<std::vector<int>> attr_params(nA);
+            for (int p = 0; p < n; ++p) attr_params[pr->param_attr[p]].push_back(p);
+            auto chain_moves = [&](int t) {
+                for (int u : chain[t])
+                    for (int k = 0; k < 9; ++k) {
+                        const int a = pr->tfm_attrs[9 * u + k];
+                        if (a >= 0 && (pr->attr_animated[a] || !attr_params[a].empty())) return true;
+                    }
+                return false;
+            };
+            std::vector<std::vector<int>> fr_obs(F);
+            for (int i = 0; i < M; ++i) fr_obs[d_frame[i]].push_back(i);
+            for (int f = 0; f < F && !why; ++f) {
+                fr_slot_off[f] = (int)slot_tf.size();
+                if (f >= nf) continue;
+                std::vector<int> sets;  // transforms, in the rows' order
+                for (int i : fr_obs[f]) {
+                    const int b = d_bnd[i];
+                    const int t = pr->tfm_parent[pr->bnd_tfm[b]];
+                    if (bnd_p4[b].w >= 0 || t < 0 || !chain_moves(t)) continue;
+                    auto it = std::find(sets.begin(), sets.end(), t);
+                    obs_bset[i] = (int)(it - sets.begin());
+                    if (it == sets.end()) sets.push_back(t);
+                }
+                for (size_t q = 0; q < sets.size(); ++q) {
+                    slot_tf.push_back(sets[q]);
+                    slot_k.push_back(-1);
+                    slot_set.push_back((int)q);
+                }
+                const int k0 = fr_par_off[f], k1 = fr_par_off[f + 1];
+                for (size_t q = 0; q < sets.size(); ++q)
+                    for (int k = k0; k < k1; ++k) {
+                        bool in_chain = false;
+                        for (int u : chain[sets[q]])
+                            for (int j = 0; j < 9; ++j)
+                                in_chain |= pr->tfm_attrs[9 * u + j] == pr->param_attr[fr_par[k]];
+                        if (!in_chain) continue;
+                        slot_tf.push_back(sets[q]);
+                        slot_k.push_back(k - k0);
+                        slot_set.push_back((int)q);
+                    }
+                if ((int)slot_tf.size() - fr_slot_off[f] > BATCH_OSLOTS)
+                    why = "more than 32 object records in one frame";
+            }
+            fr_slot_off[F] = (int)slot_tf.size();
+            static_assert(BATCH_OSLOTS == 32, "the refusal's wording");
+        }
         if (why) {
             batch_why = why;
         } else {
             batch_ok = true;
+            if (batch_obj) {
+                bobj.fr_slot_off = upload(fr_slot_off);
+                bobj.slot_tf = upload(slot_tf);
+                bobj.slot_k = upload(slot_k);
+                bobj.slot_set = upload(slot_set);
+                bobj.obs_set = upload(obs_bset);
+            }
             batch_nf = nf;
             batch_nfmax = nfmax;
             d_fr_cf_off = upload(fr_cf_off);

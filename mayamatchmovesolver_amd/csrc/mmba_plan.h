@@ -32,6 +32,10 @@ int path_choice(int key);
 // their lens instances follow the reference's one-frame solves (no index
 // mixing, Plan::build_lens_instances)
 extern thread_local bool t_lens_plain;
+// set with it by mmba_plan_create_per_frame: object-frame parameters join
+// their reading camera-frame's block wherever eligible, at any frame count
+// (what MMBA_PATH_OBJ_CF = 1 pins; MMBA_PATH_OBJ_CF = 0 still wins)
+extern thread_local bool t_obj_cf;
 
 #define MMBA_HIP(call)                                                             \
     do {                                                                           \
@@ -591,6 +595,13 @@ struct Plan {
     bool batch_ok = false;
     std::string batch_why;
     int batch_nf = 0, batch_nfmax = 0;
+    // some frame's block holds an object-frame parameter: the object form
+    // (mmba_batch_obj.hip) with the per-frame record tables bobj
+    bool batch_obj = false;
+    BatchObjDev bobj;
+    // built by mmba_plan_create_per_frame (plain lens instances, object-frame
+    // parameters in the blocks): the whole-shot compute entries refuse it
+    bool per_frame_plan = false;
     int *d_fr_cf_off = nullptr, *d_fr_par_off = nullptr, *d_fr_par = nullptr,
         *d_fr_last = nullptr, *d_fr_nobs = nullptr;
     double *d_bJ = nullptr, *d_bdist = nullptr, *d_bx = nullptr, *d_bpw = nullptr;

@@ -288,20 +288,33 @@ def comm_unique_id() -> bytes:
 
 class Solver:
     """A problem uploaded to one MI355X (``mmba_plan``); with ``comm``, this
-    shard of a frame-sharded plan (every shard passes the same problem)."""
+    shard of a frame-sharded plan (every shard passes the same problem).
+    ``per_frame=True``: the plan of per-frame mode
+    (``mmba_plan_create_per_frame``: plain lens instances, object-frame
+    parameters in the camera-frame blocks at any frame count) -- for
+    ``solve_per_frame``, ``set_attr_values``, ``param_layout`` and
+    ``reproject``; ``solve`` / ``measure`` / ``jacobian`` raise on it.
+    Unsharded only."""
 
     def __init__(self, problem: Problem, options, context: Optional[Context] = None,
-                 device: int = 0, comm: Optional[Comm] = None):
+                 device: int = 0, comm: Optional[Comm] = None, per_frame: bool = False):
+        if per_frame and comm is not None:
+            raise ValueError("a per-frame plan is unsharded: per_frame=True with comm")
         self.problem = problem
         self.options = options
         self.ctx = context or Context(device)
         self.comm = comm
+        self.per_frame = bool(per_frame)
         self._prob_c, self._keep = problem.to_ctypes()
         self._h = C.c_void_p()
-        check(lib().mmba_plan_create_sharded(self.ctx.handle, C.byref(self._prob_c),
-                                             C.byref(self.options),
-                                             comm.handle if comm is not None else None,
-                                             C.byref(self._h)))
+        if per_frame:
+            check(lib().mmba_plan_create_per_frame(self.ctx.handle, C.byref(self._prob_c),
+                                                   C.byref(self.options), C.byref(self._h)))
+        else:
+            check(lib().mmba_plan_create_sharded(self.ctx.handle, C.byref(self._prob_c),
+                                                 C.byref(self.options),
+                                                 comm.handle if comm is not None else None,
+                                                 C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -487,6 +500,13 @@ class Solver:
         v = np.ascontiguousarray(attr_values, dtype=np.float64)
         assert v.size >= np.asarray(self.problem.attr_values).size
         check(lib().mmba_plan_set_attr_values(self._h, _dp(v)))
+
+    @staticmethod
+    def batch_launches() -> int:
+        """Batched per-frame launches this process has enqueued (test hook
+        ``mmba_debug_batch_launches``): tells the one-launch path from the
+        one-plan-per-frame fallback."""
+        return int(lib().mmba_debug_batch_launches())
 
     def solve_per_frame(self, x0=None, interrupt=None):
         """Per-frame solve mode on this plan (``mmba_plan_solve_per_frame``):
