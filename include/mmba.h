@@ -484,6 +484,34 @@ int mmba_shard_layout(int32_t num_frames, int32_t num_obs, const int32_t *obs_fr
  * options are kept; the next solve / measure starts from these values. */
 int mmba_plan_set_attr_values(mmba_plan *plan, const double *attr_values);
 
+/* Plan caching, the measurements (additive: MMBA_ABI_VERSION stays 12):
+ * replace the marker positions and weights of an existing plan -- a nudged 2D
+ * track, a changed marker weight -- without building it again.  The arrays
+ * are in the caller's order and sizes, exactly as in the mmba_problem the plan
+ * was built from: obs_xy [2 * num_obs], obs_weight [num_obs], mkr_frame_xy
+ * [2 * num_markers * num_frames].  Any of them may be NULL: left as it is
+ * (all three NULL: MMBA_OK, nothing done).  The next solve / measure /
+ * reproject / Jacobian computes what a plan freshly built from the new arrays
+ * computes, bit for bit; what an earlier call left (mmba_plan_outputs,
+ * mmba_plan_error_metrics) is gone, as on a fresh plan.
+ *   Checked before anything is changed: an obs_weight entry <= 0 or NaN
+ * returns MMBA_ERR_INVALID and leaves the plan exactly as it was.
+ *   MMSG mode with markers not grouped by camera (B4): an observation then
+ * compares the x,y of another marker at its frame.  A plan built with
+ * mkr_frame_xy takes those borrowed positions from the new mkr_frame_xy and
+ * the others from the new obs_xy; on such a plan obs_xy without mkr_frame_xy
+ * is MMBA_ERR_INVALID (the borrowed positions would go stale).  A plan built
+ * without mkr_frame_xy borrows from obs_xy and needs only obs_xy.  On every
+ * other plan mkr_frame_xy is ignored.
+ *   Every kind of plan takes it: unsharded, over a multi-device context
+ * (every shard is refreshed), communicator-sharded (every rank passes the
+ * whole arrays; no collective) and per-frame (mmba_plan_create_per_frame).
+ *   Not refreshable here: marker enable flags (they change the observation
+ * list, that is the structure) and the stiffness / smoothness rows' weights,
+ * variances and values.  Those need a new plan. */
+int mmba_plan_set_marker_values(mmba_plan *plan, const double *obs_xy,
+                                const double *obs_weight, const double *mkr_frame_xy);
+
 /* One residual evaluation (measureErrors, adjust_measureErrors.cpp:523) at
  * internal parameters x.  Any output pointer may be NULL. */
 int mmba_plan_measure(mmba_plan *plan, const double *x, double *fvec_out,
@@ -644,7 +672,7 @@ int mmba_plan_solve_per_frame(mmba_plan *plan, double *x_inout, mmba_result *res
  * mmba_plan_create; MMBA_PATH_OBJ_CF = 0 still wins).  One device only
  * (MMBA_ERR_INVALID on a context of several).  The plan serves
  * mmba_plan_solve_per_frame, mmba_plan_set_attr_values,
- * mmba_plan_param_layout, mmba_plan_reproject and mmba_plan_destroy;
+ * mmba_plan_set_marker_values, mmba_plan_param_layout, mmba_plan_reproject and mmba_plan_destroy;
  * mmba_plan_solve, _measure, _jacobian and mmba_debug_damped_step return
  * MMBA_ERR_INVALID on it (its lens instances are not the whole shot's).
  * mmba_solve_per_frame builds its whole-problem attempt through this. */

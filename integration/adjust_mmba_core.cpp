@@ -439,9 +439,10 @@ std::vector<uint8_t> FlatScene::plan_key(const mmba_options &o) const {
     put(k, mkr_bnd);
     put(k, obs_marker);
     put(k, obs_frame);
-    put(k, obs_xy);
-    put(k, obs_weight);
-    put(k, mkr_frame_xy);
+    // obs_xy, obs_weight and mkr_frame_xy are values a cached plan takes anew
+    // (mmba_plan_set_marker_values); whether mkr_frame_xy is there at all
+    // decides where a B4-remapped plan borrows positions from: structure
+    k.push_back(mkr_frame_xy.empty() ? 0 : 1);
     put(k, param_attr);
     put(k, param_frame);
     put(k, param_ref_attr);
@@ -550,6 +551,9 @@ mmba_plan *Shim::plan_for(const FlatScene &scene, const mmba_problem &prob,
     for (auto it = plans_.begin(); it != plans_.end(); ++it) {
         if (it->key != key) continue;
         if (mmba_plan_set_attr_values(it->plan, prob.attr_values) != MMBA_OK) return nullptr;
+        if (mmba_plan_set_marker_values(it->plan, prob.obs_xy, prob.obs_weight,
+                                        prob.mkr_frame_xy) != MMBA_OK)
+            return nullptr;
         plans_.splice(plans_.begin(), plans_, it);
         return plans_.front().plan;
     }

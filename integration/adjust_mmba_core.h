@@ -142,7 +142,10 @@ struct FlatScene {
 
     bool build(const SolverInputs &in, SceneReader &rd);
     mmba_problem problem() const;
-    // everything a plan captures at mmba_plan_create except attr_values
+    // everything a plan captures at mmba_plan_create except what a cached
+    // plan takes anew: attr_values (mmba_plan_set_attr_values) and obs_xy,
+    // obs_weight, mkr_frame_xy (mmba_plan_set_marker_values; the key keeps
+    // whether mkr_frame_xy is present)
     std::vector<uint8_t> plan_key(const mmba_options &o) const;
 
   private:
@@ -190,8 +193,10 @@ struct Result {
 void fill_result(const mmba_result &r, Result &out);
 
 // Device context + plan cache (a solve whose structure equals a cached
-// plan's only refreshes the attribute values; the Python standard solver
-// issues many such solves, solverstandardutils.py).
+// plan's only refreshes the attribute values and the marker positions and
+// weights; the Python standard solver issues many such solves,
+// solverstandardutils.py, and an artist's nudged track or changed weight is
+// another).
 class Shim {
   public:
     ~Shim() { release(); }

@@ -47,6 +47,18 @@ using namespace mmba;
         return MMBA_ERR_INVALID;                      \
     }
 
+namespace mmba {
+int plan_set_marker_values(mmba_plan *plan, const double *obs_xy, const double *obs_weight,
+                           const double *mkr_frame_xy) {
+    MMBA_GUARD({
+        Plan &p = plan->impl;
+        MMBA_HIP(hipSetDevice(p.ctx->device));
+        p.set_marker_values(obs_xy, obs_weight, mkr_frame_xy);
+        return MMBA_OK;
+    })
+}
+}  // namespace mmba
+
 extern "C" {
 
 int mmba_abi_version(void) { return MMBA_ABI_VERSION; }
@@ -423,6 +435,31 @@ int mmba_plan_set_attr_values(mmba_plan *plan, const double *attr_values) {
         MMBA_HIP(hipStreamSynchronize(p.s));
         return MMBA_OK;
     })
+}
+
+// Everything is checked against the plan (a group's first shard: the shards
+// hold one problem) before any shard is touched, so a refused call leaves the
+// plan exactly as it was.
+int mmba_plan_set_marker_values(mmba_plan *plan, const double *obs_xy, const double *obs_weight,
+                                const double *mkr_frame_xy) {
+    if (!plan) return MMBA_ERR_INVALID;
+    const Plan &p0 = plan->group ? group_first_plan(plan)->impl : plan->impl;
+    if (obs_weight)
+        for (int i = 0; i < p0.Mg; ++i)
+            if (!(obs_weight[i] > 0.0)) {  // (NaN included, as Plan::build refuses it)
+                set_error("invalid: obs_weight must be > 0");
+                return MMBA_ERR_INVALID;
+            }
+    if (p0.mk_frame_src && obs_xy && !mkr_frame_xy) {
+        set_error("invalid: obs_xy without mkr_frame_xy on a plan built from mkr_frame_xy "
+                  "(MMSG markers not grouped by camera, B4): the positions its observations "
+                  "borrow from mkr_frame_xy would go stale");
+        return MMBA_ERR_INVALID;
+    }
+    if (!p0.mk_frame_src) mkr_frame_xy = nullptr;  // no observation reads it
+    if (!obs_xy && !obs_weight && !mkr_frame_xy) return MMBA_OK;
+    if (plan->group) return group_plan_set_marker_values(plan, obs_xy, obs_weight, mkr_frame_xy);
+    return plan_set_marker_values(plan, obs_xy, obs_weight, mkr_frame_xy);
 }
 
 int mmba_plan_solve_per_frame(mmba_plan *plan, double *x_inout, mmba_result *results,

@@ -599,6 +599,17 @@ int group_plan_set_attr_values(mmba_plan *plan, const double *attr_values) {
     return g.run(f);
 }
 
+// every shard takes the whole arrays and permutes its own and halo
+// observations through its own ref_of_dev; no collective
+int group_plan_set_marker_values(mmba_plan *plan, const double *obs_xy, const double *obs_weight,
+                                 const double *mkr_frame_xy) {
+    ShardGroup &g = *plan->group;
+    const std::function<int(int)> f = [&](int k) -> int {
+        return plan_set_marker_values(g.plans[k], obs_xy, obs_weight, mkr_frame_xy);
+    };
+    return g.run(f);
+}
+
 int group_plan_solve_per_frame(mmba_plan *plan, double *x_inout, mmba_result *results,
                                const mmba_callbacks *cb) {
     ShardGroup &g = *plan->group;

@@ -19,6 +19,12 @@ inline int nblk(long n, int bs) { return (int)((n + bs - 1) / bs); }
 void launch_param_set(hipStream_t s, const DevProblem &P, const double *x, double *ext,
                       double *ext_pert, double *step, int solver_type, double delta,
                       double eps_dif);
+// the measurements of a built plan from staged arrays in the caller's order
+// (mmba_markers.hip, k_marker_set): obs_xy / obs_sqrtw / obs_tau in device
+// order; NULL staging arrays leave theirs as they are
+void launch_marker_set(hipStream_t s, int M, const int *ref_of_dev, const int *xy_src,
+                       const double *xy, const double *fxy, const double *sqrtw,
+                       const double *obs_rs, double *obs_xy, double *obs_sqrtw, double *obs_tau);
 // Partial rows -> scalar slots in one launch (row r: partial[off, off + n),
 // sum or max, -> scalar[slot]); flag (nullable) -> scalar[flag_slot], cleared.
 struct RedRow {

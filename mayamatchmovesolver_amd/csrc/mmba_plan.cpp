@@ -145,6 +145,7 @@ Plan::~Plan() {
     if (h_seq) (void)hipHostFree(h_seq);
     if (h_pack) (void)hipHostFree(h_pack);
     if (h_met) (void)hipHostFree(h_met);
+    if (h_mk) (void)hipHostFree(h_mk);
 }
 
 static void require(bool c, const char *what) {
@@ -380,6 +381,11 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     // and lens instance (B3, from obs_marker) are its own.
     std::vector<int> obs_geo(pr->obs_marker, pr->obs_marker + M);
     std::vector<double> obs_xy_geo;  // empty: obs_xy
+    // where each observation's x,y comes from (mmba_plan_set_marker_values
+    // refreshes it from there): >= 0 an index into obs_xy, < 0 the index
+    // -(src + 1) into mkr_frame_xy; empty: its own obs_xy entry
+    std::vector<int> obs_xy_src;
+    mk_frame_src = false;
     if (opt.scene_graph_mode == MMBA_SCENE_GRAPH_MM_SCENE_GRAPH) {
         std::vector<int> flat;
         flat.reserve(nK);
@@ -394,6 +400,10 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
             if (!pr->mkr_frame_xy)
                 for (int i = 0; i < M; ++i) obs_at[{pr->obs_marker[i], pr->obs_frame[i]}] = i;
             obs_xy_geo.assign(pr->obs_xy, pr->obs_xy + 2 * (size_t)M);
+            obs_xy_src.resize(M);
+            std::iota(obs_xy_src.begin(), obs_xy_src.end(), 0);
+            mk_frame_src = pr->mkr_frame_xy != nullptr;
+            if (mk_frame_src) require((long long)nK * F <= INT_MAX, "markers x frames above 2^31");
             for (int i = 0; i < M; ++i) {
                 const int k = flat[pr->obs_marker[i]], f = pr->obs_frame[i];
                 obs_geo[i] = k;
@@ -401,6 +411,7 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
                 const double *xy;
                 if (pr->mkr_frame_xy) {
                     xy = &pr->mkr_frame_xy[2 * ((size_t)k * F + f)];
+                    obs_xy_src[i] = -(k * F + f) - 1;
                 } else {
                     auto it = obs_at.find({k, f});
                     if (it == obs_at.end())
@@ -408,6 +419,7 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
                                           "without an observation at the frame read, and no "
                                           "mkr_frame_xy"};
                     xy = &pr->obs_xy[2 * (size_t)it->second];
+                    obs_xy_src[i] = it->second;
                 }
                 obs_xy_geo[2 * i] = xy[0];
                 obs_xy_geo[2 * i + 1] = xy[1];
@@ -1434,8 +1446,14 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     D.obs_bnd = upload(d_bnd);
     D.obs_frame = upload(d_frame);
     D.obs_cam = upload(d_cam);
-    D.obs_xy = upload(d_xy);
-    D.obs_sqrtw = upload(d_sqrtw);
+    D.obs_xy = d_obs_xy = upload(d_xy);
+    D.obs_sqrtw = d_obs_sqrtw = upload(d_sqrtw);
+    if (!obs_xy_src.empty()) {
+        std::vector<int> src(M);
+        for (int i = 0; i < M; ++i) src[i] = obs_xy_src[ref_of_dev[i]];
+        d_xy_src = upload(src);
+    }
+    setup_marker_refresh(nK);
     D.cf_cam = upload(cf_cam);
     D.cf_frame = upload(cf_frame);
     D.cf_obs_off = upload(cf_obs_off);
@@ -1647,12 +1665,14 @@ void Plan::build(const mmba_problem *pr, const mmba_options *o) {
     D.rs_Aoff = nullptr;
     if (rs_on) {
         if (!D.cf_aidx) throw Unsupported{"rolling shutter needs the camera-frame table"};
-        std::vector<double> tau(M);
+        std::vector<double> tau(M), obs_rs(M);
         for (int i = 0; i < M; ++i) {
             const int r = ref_of_dev[i];
+            obs_rs[i] = pr->cam_rs_value[d_cam[i]];
             tau[i] = pr->cam_rs_value[d_cam[i]] * (0.5 - pr->obs_xy[2 * r + 1]);
         }
-        D.obs_tau = upload(tau);
+        D.obs_tau = d_obs_tau = upload(tau);
+        d_obs_rs = upload(obs_rs);  // k_marker_set recomputes tau from it
         D.cf_rs_nb = upload(cf_nb);
         std::vector<int> vx((size_t)12 * ncf, -1);
         for (int cf = 0; cf < ncf; ++cf) {

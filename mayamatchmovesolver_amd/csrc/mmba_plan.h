@@ -673,6 +673,21 @@ struct Plan {
     // one launch, one copy, one wait (sharded: the merge between them); NULL
     // members of out are skipped (a group plan's shards other than 0 pass none)
     void error_metrics(mmba_error_metrics *out);
+    // refresh of the measurements (mmba_plan_set_marker_values,
+    // mmba_markers.hip): the three device arrays P reads them through, the
+    // x,y source of every device observation where a B4 remap borrows
+    // positions (d_xy_src, nullptr: its own obs_xy entry; mk_frame_src: the
+    // borrowed ones come from mkr_frame_xy), each device observation's
+    // rolling-shutter value (rs_on), and the staging blocks in the caller's
+    // order, device and page-locked host (mk_nfxy: doubles of mkr_frame_xy)
+    double *d_obs_xy = nullptr, *d_obs_sqrtw = nullptr, *d_obs_tau = nullptr;
+    int *d_xy_src = nullptr;
+    bool mk_frame_src = false;
+    double *d_obs_rs = nullptr;
+    double *d_mk = nullptr, *h_mk = nullptr;
+    size_t mk_nfxy = 0;
+    void setup_marker_refresh(int K);
+    void set_marker_values(const double *xy, const double *weight, const double *fxy);
 };
 
 }  // namespace mmba
@@ -705,6 +720,12 @@ int group_plan_outputs(mmba_plan *plan, double *fvec_out, double *err_user_out,
 int group_plan_error_metrics(mmba_plan *plan, mmba_error_metrics *out);
 const mmba_plan *group_first_plan(const mmba_plan *plan);  // mmba_plan_param_layout
 int group_plan_set_attr_values(mmba_plan *plan, const double *attr_values);
+// the arrays are already validated; plan_set_marker_values refreshes one
+// plan (mmba_api.cpp), the group form every shard
+int plan_set_marker_values(mmba_plan *plan, const double *obs_xy, const double *obs_weight,
+                           const double *mkr_frame_xy);
+int group_plan_set_marker_values(mmba_plan *plan, const double *obs_xy, const double *obs_weight,
+                                 const double *mkr_frame_xy);
 int group_plan_solve_per_frame(mmba_plan *plan, double *x_inout, mmba_result *results,
                                const mmba_callbacks *cb);
 int group_plan_kernel_stats(mmba_plan *plan, int enable_timing, mmba_kernel_stats *out);

@@ -292,7 +292,7 @@ class Solver:
     ``per_frame=True``: the plan of per-frame mode
     (``mmba_plan_create_per_frame``: plain lens instances, object-frame
     parameters in the camera-frame blocks at any frame count) -- for
-    ``solve_per_frame``, ``set_attr_values``, ``param_layout`` and
+    ``solve_per_frame``, ``set_attr_values``, ``set_marker_values``, ``param_layout`` and
     ``reproject``; ``solve`` / ``measure`` / ``jacobian`` raise on it.
     Unsharded only."""
 
@@ -500,6 +500,26 @@ class Solver:
         v = np.ascontiguousarray(attr_values, dtype=np.float64)
         assert v.size >= np.asarray(self.problem.attr_values).size
         check(lib().mmba_plan_set_attr_values(self._h, _dp(v)))
+
+    def set_marker_values(self, obs_xy=None, obs_weight=None, mkr_frame_xy=None):
+        """Replace the marker positions and weights of this plan
+        (``mmba_plan_set_marker_values``): arrays in the order and sizes of the
+        ``Problem`` the plan was built from, None = left as it is.  The
+        ``Problem`` itself is not changed.  Sizes are checked here, before any
+        call into the library."""
+        p = self.problem
+        want = (("obs_xy", obs_xy, 2 * p.num_obs), ("obs_weight", obs_weight, p.num_obs),
+                ("mkr_frame_xy", mkr_frame_xy, 2 * p.num_markers * p.num_frames))
+        arrs = []
+        for name, a, size in want:
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+                if a.size != size:
+                    raise ValueError("%s holds %d values, the plan's problem has %d"
+                                     % (name, a.size, size))
+            arrs.append(a)
+        check(lib().mmba_plan_set_marker_values(self._h, _dp(arrs[0]), _dp(arrs[1]),
+                                                _dp(arrs[2])))
 
     @staticmethod
     def batch_launches() -> int:
