@@ -934,7 +934,12 @@ int mmba_debug_reduced_residual(mmba_plan *plan, const double *x, double lam, do
  * order: step_out [n] = p, g_out [n] = J^T f, diag_out [n] = D, and fjac_out
  * [m x n, column-major] = the dense J reassembled after the solve from what
  * the pass stored.  MMBA_ERR_INVALID when the factorisation fails (on every
- * shard together); MMBA_ERR_UNSUPPORTED for B15 plans.
+ * shard together).
+ * A B15 plan (lmder with central differences over animated parameters of
+ * several frames: J = J_s + f c^T, solved in a per-camera-frame Householder
+ * basis with a Woodbury term) hands all four back in the original basis and
+ * parameter order, of the whole J: g_out = J^T f = J_s^T f + ||f||^2 c,
+ * diag_out the norms of J's columns, fjac_out = J_s + f c^T.
  * A sharded plan runs the same calls with the solve's collectives, so every
  * shard calls together.  step_out, g_out and diag_out are whole on every
  * rank (each parameter's entry from its owner, all-gathered).  fjac_out

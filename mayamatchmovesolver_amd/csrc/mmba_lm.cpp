@@ -1486,12 +1486,19 @@ int Plan::reduced_residual(const double *x, double lam, double *relres) {
 // A sharded plan runs the same calls with the solve's collectives (every
 // shard calls together); each shard hands back its own parameters' entries
 // and its own observations' rows (Plan::handback_step).
+// A B15 plan (J = J_s + f c^T, unsharded by Plan::build) hands all four back
+// in the original basis: the step is d_xs (launch_b15_rot closes the solve),
+// g is d_g15 = u + s c (d_g holds the rotated u), D is d_diag once the
+// solve's swaps are undone (the norms of the whole J's columns) and the dense
+// J is J_s un-rotated plus f c^T.  s = ||f||^2 comes from the slot the
+// evaluation just filled, as a solve's first Jacobian reads SL_F0.
 int Plan::damped_step(const double *x, double lam, double *step_out, double *g_out,
                       double *diag_out, double *fjac_out) {
-    if (b15) throw Unsupported{"damped step hook: B15 plan"};
     const bool sharded = nranks > 1;
     // uniform fast plans store no jcol (a property of the plan): one
-    // Jacobian pass with it stored, ahead of the pass under test
+    // Jacobian pass with it stored, ahead of the pass under test.  B15 plans
+    // never take it: central differences run on the generic kernels, which
+    // store jcol (Plan::build: jcol_implicit only with jac_ncv > 0)
     bool pre = fjac_out && P.jcol_implicit && !dbg_jcol_stored;
     if (sharded) {
         // the pre-pass carries collectives (the evaluation's ||f||^2, the
@@ -1528,7 +1535,8 @@ int Plan::damped_step(const double *x, double lam, double *step_out, double *g_o
     MMBA_HIP(hipMemcpyAsync(d_x, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
     MMBA_HIP(hipMemsetAsync(d_diag, 0, sizeof(double) * n, s));
     fun(d_x, d_f, d_eu, d_ed);
-    const JacLM lm{1, 1, 1.0, nullptr};
+    // (B15: the rank-one term needs the true ||f||^2, not the placeholder norm)
+    const JacLM lm{1, 1, 1.0, b15 ? d_scalar + SL_FNORM : nullptr};
     jac(d_x, &lm);
     solve_damped_enqueue(lam, SL_DNORM);
     read_slots(SL_DNORM, SL_FAIL);
@@ -1540,13 +1548,17 @@ int Plan::damped_step(const double *x, double lam, double *step_out, double *g_o
         if (step_out)
             MMBA_HIP(hipMemcpyAsync(step_out, d_xs, sizeof(double) * n, hipMemcpyDeviceToHost, s));
         if (g_out)
-            MMBA_HIP(hipMemcpyAsync(g_out, d_g, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+            MMBA_HIP(hipMemcpyAsync(g_out, b15 ? d_g15 : d_g, sizeof(double) * n,
+                                    hipMemcpyDeviceToHost, s));
         if (diag_out)
             MMBA_HIP(hipMemcpyAsync(diag_out, d_diag, sizeof(double) * n, hipMemcpyDeviceToHost,
                                     s));
         host_sync();
     }
-    if (fjac_out)  // after the solve: what the pass itself stored
+    // after the solve: what the pass itself stored (B15: d_J is un-rotated in
+    // place, and every later entry point runs its own Jacobian pass before
+    // anything reads d_J)
+    if (fjac_out)
         assemble_dense_jacobian(fjac_out, sharded);
     else
         collect_spans();

@@ -35,14 +35,13 @@ Pairs left out (lam = 0 only), by name, in LEFT_OUT with their e64.
 Sharded and group plans: test_gpu_damped_step_sharded.py, the same reference
 and bars.
 
+B15 plans (central differences: with lmder every scene whose animated
+parameters span several frames builds a B15 plan or none, Plan::build; lmdif
+has forward differences only): test_gpu_damped_step_b15.py, the same bars
+against a yardstick in the plan's rotated basis.
+
 Not reached: k_schur_pairs (Plan::build takes it only above 2^30 destination
 pairs);
-  B15 plans: the hook refuses them -- the rotated basis and the Woodbury term
-    need a reference formulation of their own.  Central differences are among
-    them: with lmder every scene whose animated parameters span several
-    frames builds a B15 plan or none (Plan::build), the C4 and C2 windows of
-    test_gpu_b15.py included (test_gpu_damped_step_sharded.py asserts the
-    refusal), and lmdif has forward differences only;
   per-frame batch plans: mmba_plan_solve_per_frame runs its own batched LM
     (mmba_batch.hip), which has no single damped step to hand back.
 

@@ -45,6 +45,10 @@ test_group_fused_jacobian_shards keeps that path at its whole-solve bar.
 
 Pairs left out (lam = 0 only), in LEFT_OUT with their e64 on the oracle's J.
 
+B15 plans (lmder with central differences over animated parameters of several
+frames) are unsharded by Plan::build; their step is held to the same bars in
+test_gpu_damped_step_b15.py.
+
 Measured on an MI355X, e64 / the device's error (the step measure, on the
 merged device J; g and D stayed below 2e-4 of their bars everywhere; the ring
 order gave the same figures to two digits; every run prints these lines with
@@ -453,23 +457,3 @@ def test_hook_refusals_and_repeats(paths):
         for u, v, w in zip(a, b, c):
             np.testing.assert_array_equal(u, v)
             np.testing.assert_array_equal(u, w)
-
-
-@gpu
-@pytest.mark.parametrize("index,kw", [(3, dict(frames=8, scale=0.001)),
-                                      (1, dict(frames=8, scale=0.1))], ids=["c4", "c2"])
-def test_b15_still_refused(index, kw, gpu_ctx):
-    """Central differences over animated parameters build a B15 plan (J = J_s
-    + f c^T): the hook refuses it, on the C4 and C2 windows of test_gpu_b15.py
-    -- which is why no central scene stands in the harness."""
-    from mayamatchmovesolver_amd._lib import MmbaError
-    prob = S.make_config(index, **kw)
-    opt = S.config_options(prob, auto_diff_type=abi.AUTO_DIFF_TYPE_CENTRAL)
-    s = Solver(prob, opt, context=gpu_ctx)
-    try:
-        with pytest.raises(MmbaError) as e:
-            s.damped_step(prob.x0, 1.0)
-        assert e.value.code == abi.MMBA_ERR_UNSUPPORTED
-        assert "B15" in str(e.value)
-    finally:
-        s.close()
